@@ -27,6 +27,13 @@ the slowest rank's matcher kernel time). The same run then times the weak form
 keys, no data-path collective) and prints it beside the headline as
 `weak_value` / `weak`. --strong / --weak run one form only. C1 (no partition)
 runs replicas; C4 runs its streaming path per rank (main_c4).
+
+A plain run sets up, warms up, times --steps steps and prints the result line.
+--full adds what the headline figure does not need: the CPU baseline on a sample
+of the stream and the check of the whole output against the vectorised
+restatement (C4: the oracle's digest). --dump-outputs DIR writes the last timed
+step's ordered output (a fixed sample of its rows when large) as .npy arrays; the
+streams are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -52,6 +59,14 @@ def parse():
                     help="CPU baseline threads for partitioned configs without timers (events split by key; "
                          "0 = 1 thread, except C5: min(16, nproc))")
     ap.add_argument("--no-verify", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline (--cpu-sample) and the "
+                         "check of the output against the vectorised restatement / the oracle's digest "
+                         "(--no-verify skips it). A plain run only sets up, warms up, times the steps and prints "
+                         "the result line, with `cpu_baseline` and `verified_vs_restatement` null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to DIR/<name>.npy "
+                         "(float32 / float64; a fixed seeded sample of the rows when the output is large)")
     ap.add_argument("--agg", action="store_true",
                     help="c2 / c3: SURVEY.md 8d select variant (ii), the projection + sum / avg aggregators")
     ap.add_argument("--columns", action="store_true",
@@ -91,6 +106,9 @@ def parse():
             args.rate = 1000
     if args.config == "c4" and args.keys == 10_000:
         args.keys = 10_000_000
+    if not args.full:
+        # a plain run: the headline figure only
+        args.no_verify, args.cpu_sample = True, 0
     return args
 
 
@@ -300,12 +318,18 @@ def main_c4(args, torch, dist, world, rank, dev):
         dist.all_reduce(dt_t[:1], op=dist.ReduceOp.MAX, group=group)
         dist.all_reduce(dt_t[1:], op=dist.ReduceOp.SUM, group=group)
     tot, m = float(dt_t[0].item()), int(dt_t[1].item())
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        # rank 0's drained rows of the last step
+        out = last["out"]
+        rows = dump_sample(len(out["seq"]))
+        dump_outputs(args.dump_outputs, len(out["seq"]), rows, out["seq"][rows], out["values"][rows],
+                     list(c.queries[0].out_types), out["query"][rows])
     # strong: the one stream over all ranks; weak: every rank's own stream
     value = (n if strong else n * world) * args.steps / tot
     # the ordered output vs the oracle's digest on the same stream (tests/golden/
     # c4_digest.json, tests/golden/make_c4_digest.py), when it holds this workload
     verified = None
-    if (world == 1 or not strong) and not args.c4_calls:
+    if args.full and (world == 1 or not strong) and not args.c4_calls:
         try:
             from c4_cases import c4_digest
             key = ("every" if args.c4_every else "default") + f"_{args.events}_{args.keys}"
@@ -435,6 +459,43 @@ def cpu_baseline(args, W, n):
 
 BATCH = 4096  # events per send(Event[]) call
 
+DUMP_ROWS = 1 << 19  # --dump-outputs keeps at most this many rows (about 40 MB with six select values)
+DUMP_SEED = 20261019
+
+
+def dump_sample(m):
+    """row indices --dump-outputs keeps of an m-row output: every row, or a fixed
+    seeded sample of DUMP_ROWS rows in row order"""
+    if m <= DUMP_ROWS:
+        return np.arange(m, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(m, DUMP_ROWS, replace=False))
+
+
+def dump_outputs(path, m, rows, seq, vals, types, query=None):
+    """--dump-outputs: the kept rows of the last timed step's ordered output as
+    float64 arrays (exact: sequence numbers and longs of these workloads are below
+    2^53, float select values widen from their f32 bits). `vals` holds the raw
+    8-byte row values (sh_vm.h load_attr), `types` the select attributes' types."""
+    from siddhi_amd import compiler as cp
+    out = np.empty(vals.shape, np.float64)
+    for o in range(vals.shape[1]):
+        c = np.ascontiguousarray(vals[:, o]).astype(np.int64, copy=False)
+        t = types[o] if o < len(types) else cp.LONG
+        if t == cp.FLOAT:
+            out[:, o] = (c & 0xFFFFFFFF).astype(np.uint32).view(np.float32)
+        elif t == cp.DOUBLE:
+            out[:, o] = c.view(np.float64)
+        else:
+            out[:, o] = c
+    os.makedirs(path, exist_ok=True)
+    arrays = {"n_matches": np.array([m], np.float64), "rows": rows.astype(np.float64),
+              "trigger_seq": np.asarray(seq).astype(np.float64), "values": out}
+    if query is not None:
+        arrays["query"] = np.asarray(query).astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    log(f"wrote {len(rows)} of {m} rows to {path}")
+
 
 def main_sharded(args, torch, dist, world, rank, dev):
     """C2 / C3 / C5 over `world` GPUs: one stream, key-sharded step (module docstring)."""
@@ -507,6 +568,13 @@ def main_sharded(args, torch, dist, world, rank, dev):
     kmax = float(allr[:, 3].max())
     achieved = float(b_alg.sum()) / world / (kmax / 1000.0)
     peak = 8.0e12
+    if args.dump_outputs and rank == 0:
+        # rank 0's ordered rows (the matches its slice's events triggered)
+        rows = dump_sample(int(seq.numel()))
+        sel = torch.from_numpy(rows).to(dev)
+        v = vals[sel].cpu().numpy()
+        dump_outputs(args.dump_outputs, int(seq.numel()), rows, seq[sel].cpu().numpy(), v[:, :-1] if wq else v,
+                     runner.out_types, v[:, -1] if wq else None)
     verified = None
     if not args.no_verify and rank == 0:
         log("verifying rank 0's ordered rows against the vectorised restatement")
@@ -686,23 +754,33 @@ def run_partitions(args, torch, dist, world, rank, dev):
     achieved = b_alg / (step_kernels_ms / 1000.0)
     match_only = b_alg / (adv_ms / 1000.0)
 
-    verified = None
-    if not args.no_verify and rank == 0:
-        log("verifying the full output against the vectorised restatement")
+    def host_rows(sel=None):
+        """the last step's output on the host as (trigger_seq, raw 8-byte row values,
+        query or None); `sel`: only these rows (an index tensor on the device)"""
+        pick = (lambda t: t) if sel is None else (lambda t: t[sel])
         if use_packed:
-            import numpy as np
             from siddhi_amd.device_run import packed_to_raw
             offs, rb = runner.packed_layout()
-            oseq_np, ovals_np = packed_to_raw(ovals.cpu().numpy(), runner.out_types, offs, rb)
+            oseq_np, ovals_np = packed_to_raw(pick(ovals).cpu().numpy(), runner.out_types, offs, rb)
             oseq_np = oseq_np.view(np.int64)
         elif use_cols:
             from siddhi_amd.device_run import columns_to_raw
-            ovals_np = columns_to_raw([c.cpu().numpy() for c in ovals], runner.out_types)
-            oseq_np = oseq.cpu().numpy()
+            ovals_np = columns_to_raw([pick(c).cpu().numpy() for c in ovals], runner.out_types)
+            oseq_np = pick(oseq).cpu().numpy()
         else:
-            ovals_np = ovals.cpu().numpy()
-            oseq_np = oseq.cpu().numpy()
-        verified = check_rows(W, oseq_np, ovals_np, oq.cpu().numpy() if oq is not None else None)
+            ovals_np = pick(ovals).cpu().numpy()
+            oseq_np = pick(oseq).cpu().numpy()
+        return oseq_np, ovals_np, pick(oq).cpu().numpy() if oq is not None else None
+
+    if args.dump_outputs and rank == 0:
+        rows = dump_sample(int(m))
+        s_seq, s_vals, s_q = host_rows(torch.from_numpy(rows).to(dev))
+        dump_outputs(args.dump_outputs, int(m), rows, s_seq, s_vals, runner.out_types, s_q)
+
+    verified = None
+    if not args.no_verify and rank == 0:
+        log("verifying the full output against the vectorised restatement")
+        verified = check_rows(W, *host_rows())
 
     # HBM bytes per step from the committed rocprofv3 PMC passes of this exact
     # workload and variant (scripts/pmc_traffic.py): config, events, keys, --agg,

@@ -9,7 +9,7 @@ mkdir -p gpurun_out/$name
 for r in 1 2; do
   for arm in A B; do
     e=$ea; [ $arm = B ] && e=$eb
-    v="--no-verify"; [ $arm = B ] && [ $r = 1 ] && v=""
+    v="--no-verify"; [ $arm = B ] && [ $r = 1 ] && v="--full"
     env $e timeout -k 10 300 python -u bench.py --cpu-sample 0 $v "$@" \
         > gpurun_out/$name/$arm$r.json 2> gpurun_out/$name/$arm$r.err || { tail -20 gpurun_out/$name/$arm$r.err; exit 1; }
     python -c "import json; d=json.loads(open('gpurun_out/$name/$arm$r.json').read().strip().splitlines()[-1]); p=d.get('phase_ms') or {}; print('$arm$r', '$e', round(d['ms_per_step'],3), 'verified', d.get('verified_vs_restatement'), {k: round(v,3) for k,v in p.items() if v})"

@@ -12,11 +12,11 @@ set -o pipefail
 A="--steps 1 --warmup 0 --cpu-sample 0 --no-verify"
 case $1 in
 bench)
-    scripts/gpu.sh bench c2 --config c2 --steps 20 --warmup 3 \
-    && scripts/gpu.sh bench c3 --config c3 --steps 10 --warmup 2 \
-    && scripts/gpu.sh bench c5 --config c5 --steps 5 --warmup 2 \
-    && scripts/gpu.sh bench c2agg --config c2 --agg --steps 10 --warmup 2 --cpu-sample 0 \
-    && scripts/gpu.sh bench c4 --config c4 --steps 1 --warmup 0
+    scripts/gpu.sh bench c2 --full --config c2 --steps 20 --warmup 3 \
+    && scripts/gpu.sh bench c3 --full --config c3 --steps 10 --warmup 2 \
+    && scripts/gpu.sh bench c5 --full --config c5 --steps 5 --warmup 2 \
+    && scripts/gpu.sh bench c2agg --full --config c2 --agg --steps 10 --warmup 2 --cpu-sample 0 \
+    && scripts/gpu.sh bench c4 --full --config c4 --steps 1 --warmup 0
     ;;
 prof)
     for c in c2 c3 c5; do scripts/gpu.sh prof ${c}prof --config $c --steps 5 --warmup 1 --cpu-sample 0 --no-verify || exit 1; done
@@ -33,7 +33,7 @@ pmc)
     ;;
 rehearse)
     R="python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1"
-    SH_BENCH_SHARE_GPU=1 timeout -k 10 600 $R --master-port 29533 bench.py --gpus 2 --config c2 --steps 5 --warmup 1 \
+    SH_BENCH_SHARE_GPU=1 timeout -k 10 600 $R --master-port 29533 bench.py --full --gpus 2 --config c2 --steps 5 --warmup 1 \
         --cpu-sample 0 > gpurun_out/reh_c2.json 2> gpurun_out/reh_c2.err \
     && SH_BENCH_SHARE_GPU=1 timeout -k 10 600 $R --master-port 29534 bench.py --gpus 2 --config c4 --c4-calls 3000 \
         --steps 1 --warmup 0 --cpu-sample 0 > gpurun_out/reh_c4.json 2> gpurun_out/reh_c4.err
