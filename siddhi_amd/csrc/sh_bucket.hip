@@ -532,10 +532,10 @@ __global__ void __launch_bounds__(BK_TPB, BK_OCC) k_bk_emit(shb_plan P, shb_out 
 // hstart[T] <- the first halo tile of a matcher pass whose chunk starts at tile
 // T: tile T - 1, and before it every tile whose successor starts within W of
 // tile T's first event (for streams in time order, every tile that can hold an
-// event the window reaches), at most SHB_HMAX. One thread per tile.
-__global__ void __launch_bounds__(256) k_bk_halo(const int64_t* __restrict__ tfirst, int32_t* __restrict__ hstart,
-                                                 int32_t nt, int64_t within) {
-    const int t = blockIdx.x * 256 + threadIdx.x;
+// event the window reaches), at most SHB_HMAX. One thread per tile (a role of
+// k_bk_prep_a).
+__device__ __forceinline__ void bk_halo(const int64_t* __restrict__ tfirst, int32_t* __restrict__ hstart, int32_t nt,
+                                        int64_t within, int t) {
     if (t >= nt) return;
     const int64_t ta = tfirst[t];
     const int64_t tlim = ta < INT64_MIN + within ? INT64_MIN : ta - within;
@@ -547,9 +547,9 @@ __global__ void __launch_bounds__(256) k_bk_halo(const int64_t* __restrict__ tfi
 // tpre[T] <- the latest timestamp of the tiles before T (exclusive prefix max,
 // INT64_MIN for tile 0): the matcher's proof that a walk leaving its key's run
 // saw every event of the key inside the window. One workgroup, each thread a
-// contiguous run of tiles (independent loads), one LDS scan.
-__global__ void __launch_bounds__(1024) k_bk_tpre(int64_t* __restrict__ tpre, int32_t nt) {
-    __shared__ int64_t s[1024];
+// contiguous run of tiles (independent loads), one LDS scan (a role of
+// k_bk_prep_b; s: 1,024 words of LDS).
+__device__ __forceinline__ void bk_tpre(int64_t* __restrict__ tpre, int32_t nt, int64_t* s) {
     const int per = (nt + 1023) / 1024;
     const int t0 = threadIdx.x * per;
     int64_t m = INT64_MIN;
@@ -1415,20 +1415,63 @@ static int bk_ok() { return hipGetLastError() == hipSuccess ? 0 : -3; }
 
 // the tiles' bucket starts transposed (bucket-major): a matcher workgroup reads its
 // bucket's starts over ~180 tiles as one contiguous run instead of one cache line
-// per tile (64 tiles per workgroup, staged in LDS)
+// per tile (64 tiles per workgroup, staged in LDS). With tpfx, also the exclusive
+// prefix of each bucket's segment lengths inside the block's 64 tiles (one wave
+// per bucket: a tile per lane) and the block's total per bucket (tpfb, scanned by
+// k_bk_prep_b): the matcher's segment table without a scan of its own.
+// Workgroups past the nbt transpose blocks take the halo bounds, 1,024 tiles each
+// (the roles are independent of each other: one launch).
 #define TT_T 64
-__global__ void __launch_bounds__(256) k_bk_toff_t(const uint16_t* __restrict__ toff, int nt,
-                                                   uint16_t* __restrict__ tofft, int stride) {
+__global__ void __launch_bounds__(1024) k_bk_prep_a(const uint16_t* __restrict__ toff, int nt,
+                                                    uint16_t* __restrict__ tofft, int stride,
+                                                    uint32_t* __restrict__ tpfx, uint32_t* __restrict__ tpfb, int nbt,
+                                                    const int64_t* __restrict__ tfirst, int32_t* __restrict__ hstart,
+                                                    int64_t within) {
     __shared__ uint16_t s[TT_T][SHB_NB + 2];
+    if ((int)blockIdx.x >= nbt) {
+        bk_halo(tfirst, hstart, nt, within, ((int)blockIdx.x - nbt) * 1024 + (int)threadIdx.x);
+        return;
+    }
     const int T0 = (int)blockIdx.x * TT_T;
-    for (int i = threadIdx.x; i < TT_T * (SHB_NB + 1); i += 256) {
+    for (int i = threadIdx.x; i < TT_T * (SHB_NB + 1); i += 1024) {
         const int t = i / (SHB_NB + 1), b = i - t * (SHB_NB + 1);
         s[t][b] = T0 + t < nt ? toff[(int64_t)(T0 + t) * SHB_TOFF + b] : (uint16_t)0;
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < (SHB_NB + 1) * TT_T; i += 256) {
-        const int b = i / TT_T, t = i - b * TT_T;
-        if (T0 + t < nt) tofft[(int64_t)b * stride + T0 + t] = s[t][b];
+    static_assert(TT_T == 64, "a tile per lane");
+    const int t = (int)(threadIdx.x & 63u);
+    for (int b = (int)(threadIdx.x >> 6); b < SHB_NB + 1; b += 1024 / 64) {
+        const uint32_t lo = s[t][b];
+        if (T0 + t < nt) tofft[(int64_t)b * stride + T0 + t] = (uint16_t)lo;
+        if (tpfx && b < SHB_NB) {
+            const uint32_t len = (uint32_t)s[t][b + 1] - lo;  // (tiles past nt: 0)
+            const uint32_t incl = shw_incl_scan(len);
+            if (T0 + t < stride) tpfx[(int64_t)b * stride + T0 + t] = incl - len;
+            if (t == 63) tpfb[(int64_t)b * (nbt + 1) + blockIdx.x] = incl;
+        }
+    }
+}
+
+// tpfb[b][0 .. nbt] <- the exclusive prefix of bucket b's block totals (in place;
+// [nbt]: the bucket's events), one wave per bucket. Workgroup 0 takes tpre when
+// the stream has timestamps (independent of the scan: one launch).
+__global__ void __launch_bounds__(1024) k_bk_prep_b(uint32_t* __restrict__ tpfb, int nbt, int64_t* __restrict__ tpre,
+                                                    int32_t nt, int ntp) {
+    __shared__ int64_t s[1024];
+    if ((int)blockIdx.x < ntp) {
+        bk_tpre(tpre, nt, s);
+        return;
+    }
+    const int b = ((int)blockIdx.x - ntp) * (1024 / 64) + (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63u);
+    if (b >= SHB_NB) return;  // (whole waves)
+    uint32_t* row = tpfb + (int64_t)b * (nbt + 1);
+    uint32_t carry = 0;
+    for (int base = 0; base <= nbt; base += 64) {
+        const int i = base + lane;
+        const uint32_t v = i < nbt ? row[i] : 0u;
+        const uint32_t incl = shw_incl_scan(v);
+        if (i <= nbt) row[i] = carry + incl - v;
+        carry += shw_last(incl);
     }
 }
 
@@ -1439,13 +1482,17 @@ extern "C" int shb_partition(const int32_t* keys, const int64_t* ts, int32_t nke
     hipLaunchKernelGGL((k_bk_scatter<2, 1024>), dim3(bk_grid(P->nt)), dim3(1024), 0, st, keys, ts, nkeys, *P);
     if (bk_ok()) return -3;
     if (P->tstride < P->nt) return -1;
-    hipLaunchKernelGGL(k_bk_toff_t, dim3((P->nt + TT_T - 1) / TT_T), dim3(256), 0, st, (const uint16_t*)P->toff, P->nt,
-                       P->tofft, P->tstride);
-    if (!P->no_ts) {
-        hipLaunchKernelGGL(k_bk_halo, dim3((P->nt + 255) / 256), dim3(256), 0, st, P->tfirst, P->hstart, P->nt,
-                           P->within);
-        hipLaunchKernelGGL(k_bk_tpre, dim3(1), dim3(1024), 0, st, P->tpre, P->nt);
-    }
+    // two launches: the transpose (+ the segment prefixes when the plan has them) with
+    // the halo bounds, then the prefix of the block totals with tpre
+    const int nbt = (P->nt + TT_T - 1) / TT_T, ntp = P->no_ts ? 0 : 1;
+    const bool pfx = P->tpfx && P->tpfb;
+    if (pfx && P->tstride != nbt * TT_T) return -1;
+    hipLaunchKernelGGL(k_bk_prep_a, dim3(nbt + (P->no_ts ? 0 : (P->nt + 1023) / 1024)), dim3(1024), 0, st,
+                       (const uint16_t*)P->toff, P->nt, P->tofft, P->tstride, pfx ? P->tpfx : nullptr,
+                       pfx ? P->tpfb : nullptr, nbt, P->tfirst, P->hstart, P->within);
+    if (ntp || pfx)
+        hipLaunchKernelGGL(k_bk_prep_b, dim3(ntp + (pfx ? SHB_NB / (1024 / 64) : 0)), dim3(1024), 0, st, P->tpfb, nbt,
+                           P->tpre, P->nt, ntp);
     return bk_ok();
 }
 

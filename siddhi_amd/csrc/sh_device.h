@@ -126,6 +126,10 @@ struct shb_plan {
     uint16_t* tofft;          // the same transposed, [SHB_NB + 1][tstride]: a bucket's starts over the tiles
     int32_t tstride;          // (contiguous for the matchers, which read one bucket over many tiles)
     int32_t pad_t;
+    // a bucket's segment lengths (toff[T][b + 1] - toff[T][b]) summed over the tiles before T,
+    // in two levels: tile T's prefix = tpfx[b][T] + tpfb[b][T >> 6] (both NULL: not built)
+    uint32_t* tpfx;           // [SHB_NB][tstride]: exclusive prefix inside the tile's block of 64 tiles
+    uint32_t* tpfb;           // [SHB_NB][tstride / 64 + 1]: exclusive prefix of the blocks' totals (+ the total)
     uint8_t* cnt;             // tiles' bucket order: partials consumed per event
     uint32_t* mstart;         // [nt][SHB_NB]: match-stream position of each (tile, bucket) segment's first match
     uint32_t* ttot;           // [nt + 1]: matches per arrival tile -> exclusive scan

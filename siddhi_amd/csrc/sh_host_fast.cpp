@@ -635,6 +635,13 @@ int run_bucket(sh_handle* h, sh_device_run* run, int32_t nkeys, bool force_carry
     B.tstride = (B.nt + 63) & ~63;
     if (h->bk_tofft.ensure_fresh((int64_t)(SHB_NB + 1) * B.tstride * 2)) return fail(h, SH_E_OOM, "bucket workspace");
     B.tofft = h->bk_tofft.as<uint16_t>();
+    // the matcher's segment table: each bucket's segment lengths summed over the tiles,
+    // written once per step by the partition (12.5 MB at 100M events)
+    if (h->bk_tpfx.ensure_fresh((int64_t)SHB_NB * B.tstride * 4) ||
+        h->bk_tpfb.ensure_fresh((int64_t)SHB_NB * (B.tstride / 64 + 1) * 4))
+        return fail(h, SH_E_OOM, "bucket workspace");
+    B.tpfx = h->bk_tpfx.as<uint32_t>();
+    B.tpfb = h->bk_tpfb.as<uint32_t>();
     B.cnt = h->bk_cnt.as<uint8_t>();
     B.mstart = h->bk_mstart.as<uint32_t>();
     B.tpre = h->bk_tpre.as<int64_t>();

@@ -331,7 +331,7 @@ struct sh_handle {
     int s3b_last = 0;         // 1: ... on the sequence bucket-carry engine (k_s3b)
     shj_bucket bk{};
     std::string bk_err;
-    DevBuf bk_w0, bk_sp, bk_toff, bk_tofft, bk_cnt, bk_mstart, bk_tpre, bk_tfirst, bk_hstart, bk_ttot, bk_flag, bk_prof;
+    DevBuf bk_w0, bk_sp, bk_toff, bk_tofft, bk_tpfx, bk_tpfb, bk_cnt, bk_mstart, bk_tpre, bk_tfirst, bk_hstart, bk_ttot, bk_flag, bk_prof;
     DevBuf bk_st[SHB_MAX_STAGED], bk_ms[SHB_MAX_MS], bk_agg[SHB_MAX_AGG];
     bool bk_agg_carried = false;  // the last bucketed run carried its aggregates (k_bk_aggc)
     PinBuf bk_rd;

@@ -1047,11 +1047,18 @@ uint16_t* const s_msk = (uint16_t*)u_buf;
 static_assert((SHB_TPB / 64) * 256 * 4 >= SHB_CHJ * 2, "masks fit u_buf");
 // run: halo events per local key, then their inclusive prefix over the keys
 __shared__ uint32_t run[256], tstart[256], ws[SHB_TPB / 64];
-// the pass's segments, one per tile from the first halo tile: start in span
-// order (exclusive prefix of the lengths, from the table's first tile) and the
-// global index of the first event; seg_of[j]: segment of span event 32 j
-__shared__ uint32_t seg_p[SHB_NSEG + 1];
-__shared__ uint32_t seg_g[SHB_NSEG];
+// the workgroup's segment table, loaded once: per tile of [A - SHB_HMAX, E] the
+// bucket's events in the tiles before it (the partition's prefix, P.tpfx + P.tpfb)
+// and per tile of [A - SHB_HMAX, E) the global index of its segment's first
+// event; per chunk tile the halo start (k_bk_prep_a: tile a - 1 and the tiles
+// before it that the window can reach). A pass's segments are a slice of the
+// table (seg_p, seg_g below); seg_of[j]: segment of span event 32 j
+__shared__ uint32_t tb_p[SHB_NSEG + 1];
+__shared__ uint32_t tb_g[SHB_NSEG];
+__shared__ int32_t tb_h[SHB_CT_MAX];
+// the latest timestamp before each table tile (k_bk_prep_b's tpre): with it in the
+// one load, a pass waits for no global load before its span's
+__shared__ int64_t tb_t[SHB_NSEG];
 __shared__ uint8_t seg_of[SHB_SPANJ / 32];
 __shared__ int s_i[2];
 )";
@@ -1072,45 +1079,44 @@ const int E = A + P.ct < P.nt ? A + P.ct : P.nt;
 const int kb = P.kb;
 const uint32_t kmask = (1u << kb) - 1u;
 const int lane = (int)(threadIdx.x & 63u), wv = (int)(threadIdx.x >> 6);
+unsigned long long t_prev = wall_clock64();  // (the table load counts with the first pass's table phase)
+const int T0 = A - SHB_HMAX;  // the table's first tile (entries of tiles < 0 are never read)
+{
+    const int Tm = T0 + (int)threadIdx.x;
+    if (Tm >= 0 && Tm <= E) {
+        // (tile tstride, one past the last block: the bucket's total alone)
+        const uint32_t in = Tm < P.tstride ? P.tpfx[(int64_t)b * P.tstride + Tm] : 0u;
+        tb_p[threadIdx.x] = in + P.tpfb[(int64_t)b * (P.tstride / 64 + 1) + (Tm >> 6)];
+        if (Tm < E) {
+            tb_g[threadIdx.x] = ((uint32_t)Tm << SHB_TILE_SHIFT) + P.tofft[(int64_t)b * P.tstride + Tm];
+            tb_t[threadIdx.x] = P.tpre[Tm];
+        }
+    }
+    if (A + (int)threadIdx.x < E) tb_h[threadIdx.x] = P.hstart[A + (int)threadIdx.x];
+}
 for (int a = A; a < E;) {
 __syncthreads();
-unsigned long long t_prev = wall_clock64();
+if (a != A) t_prev = wall_clock64();
 #define SHB_PROF(ph) if (P.prof && threadIdx.x == 0) { const unsigned long long t_now = wall_clock64(); atomicAdd(&P.prof[ph], t_now - t_prev); t_prev = t_now; }
-// the halo start (k_bk_tpre: tile a - 1 and the tiles before it that the window
-// can reach) and the bucket starts of tiles [a - SHB_HMAX, E), loaded together
-if (threadIdx.x == 0) s_i[0] = P.hstart[a];
-const int Tm = a - SHB_HMAX + (int)threadIdx.x;
-uint32_t len = 0u, g = 0u;
-if (Tm >= 0 && Tm < E) {
-    const uint32_t lo = P.tofft[(int64_t)b * P.tstride + Tm], hi = P.tofft[(int64_t)(b + 1) * P.tstride + Tm];
-    len = hi - lo;
-    g = ((uint32_t)Tm << SHB_TILE_SHIFT) + lo;
-
-)";
-    src += R"(}
-__syncthreads();
-const int h0 = s_i[0];  // first tile of the segment table
+// the pass's segments, one per tile from the first halo tile h0: seg_p[t] the
+// events of the bucket before segment t (only differences are used), seg_g[t] the
+// global index of its first event
+const int h0 = tb_h[a - A];
 const int nseg = E - h0;
-{
-    if (Tm < h0) len = 0u;
-    uint32_t tot;
-    const uint32_t pre = shw_block_excl<SHB_TPB>(len, ws, &tot);
-    if (Tm >= h0 && Tm < E) {
-        seg_p[Tm - h0] = pre;
-        seg_g[Tm - h0] = g;
-    }
-    if (Tm == E) seg_p[nseg] = tot;
-}
-__syncthreads();
+const uint32_t* const seg_p = tb_p + (h0 - T0);
+const uint32_t* const seg_g = tb_g + (h0 - T0);
 // this pass: consumers from tiles [a, a + ne), at most SHB_CHJ events; the halo
 // from segment sb on (trimmed at the front when it and tile a overflow the span)
 const int ta = a - h0;
 const uint32_t pa = seg_p[ta];
-const int sb = __syncthreads_count((int)threadIdx.x < ta && seg_p[ta + 1] - seg_p[threadIdx.x] > SHB_SPANJ);
+// (both counts by every wave for itself, over the at most SHB_HMAX halo and
+// SHB_CT_MAX chunk segments: the table is read-only here, so no barrier)
+int sb = 0, ne = 0;
+for (int x = lane; x - lane < ta; x += 64)
+    sb += (int)__popcll(__ballot(x < ta && seg_p[ta + 1] - seg_p[x] > SHB_SPANJ));
 const uint32_t sbase = seg_p[sb];
-const int ne = __syncthreads_count((int)threadIdx.x >= ta && (int)threadIdx.x < nseg &&
-                                   seg_p[threadIdx.x + 1] - pa <= SHB_CHJ &&
-                                   seg_p[threadIdx.x + 1] - sbase <= SHB_SPANJ);
+for (int x = ta + lane; x - lane < nseg; x += 64)
+    ne += (int)__popcll(__ballot(x < nseg && seg_p[x + 1] - pa <= SHB_CHJ && seg_p[x + 1] - sbase <= SHB_SPANJ));
 if (ne == 0) {
     // tile a's segment alone exceeds a chunk
     if (threadIdx.x == 0) atomicOr(P.flag, SHB_F_SPAN);
@@ -1123,17 +1129,14 @@ const int L = (int)(seg_p[se] - sbase), hl = (int)(pa - sbase), nc = L - hl;
 // a walk that leaves its key's run in the span while still in the window could
 // have missed earlier events of the key only if some event before the span is
 // as late as the window's start (tpre: the latest timestamp before each tile)
-const int64_t tmx_ = hs > 0 ? P.tpre[hs] - P.tbase : INT64_MIN;
+const int64_t tmx_ = hs > 0 ? tb_t[hs - T0] - P.tbase : INT64_MIN;
 #define SHB_OFF(t32) ((int64_t)(t32) - SHJ_W <= tmx_)
-for (int j = (int)threadIdx.x; j * 32 < L; j += SHB_TPB) {
-    const uint32_t e = sbase + (uint32_t)j * 32u;
-    int lo = sb, hi = se - 1;  // the last segment starting at or before e
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (seg_p[mid] <= e) lo = mid;
-        else hi = mid - 1;
-    }
-    seg_of[j] = (uint8_t)lo;
+// seg_of by the segments themselves: a segment owns the 32-event blocks whose
+// first event lies in it (the last segment starting at or before that event;
+// an empty segment owns none)
+for (int t = sb + (int)threadIdx.x; t < se; t += SHB_TPB) {
+    const uint32_t x1 = seg_p[t + 1] - sbase;
+    for (uint32_t j = (seg_p[t] - sbase + 31u) >> 5; j * 32u < x1; j++) seg_of[j] = (uint8_t)t;
 }
 __syncthreads();
 SHB_PROF(5)
