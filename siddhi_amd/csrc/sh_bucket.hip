@@ -1134,7 +1134,7 @@ __global__ void __launch_bounds__(AGC_TPB) k_bk_aggc(shb_plan P, shb_aggc A) {
 // :167-185, AvgAttributeAggregatorExecutor.java:145-155); a row that fails the test
 // sets SHB_F_AGG and the host takes the post-pass.
 #define AGP_ROWS 8192
-#define AGP_LIM 9007199254740992.0  // 2^53
+#define AGP_LIM 9007199254740992.0  // 2^53 (NaN, +-inf, subnormals, FLT_MAX, 2^-25 fail agp_units: DESIGN.md "Values")
 
 // output o's mode: 0 long wrap-around sum, 1 fixed-point double sum (avg: / count), 2 count
 __device__ __forceinline__ int agp_mode(const shb_aggc& A, int o, int* type) {

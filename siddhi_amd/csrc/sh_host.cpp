@@ -1339,6 +1339,7 @@ static int run_device_impl(sh_handle* h, sh_device_run* run) {
     // were written there (the handle's own stream is non-blocking and would not
     // wait for them)
     h->stream = (hipStream_t)run->stream;
+    bool rules_seq = false;  // a rule set's aggregates left the post-pass for the general engine
     if (h->has_rules && (h->mode == 2 || !getenv("SH_DISABLE_RULES"))) {
         const int crc = rows_for_cols(h, run);
         if (crc) return crc;
@@ -1352,6 +1353,8 @@ static int run_device_impl(sh_handle* h, sh_device_run* run) {
         if (h->mode == 2)
             return fail(h, SH_E_UNSUPPORTED, "rule set aggregates are not exact in parallel and the set is "
                                              "beyond the general engine's query table");
+        rules_seq = true;
+        h->rs_last = 0;  // (the rows below are the general engine's)
     }
     if (h->mode == 1) {
         // general engine from fresh per-key state; the events arrive as send()
@@ -1380,7 +1383,7 @@ static int run_device_impl(sh_handle* h, sh_device_run* run) {
         }
         int rc = SH_OK;
         int64_t rows = 0;
-        h->agg_last = 0;
+        h->agg_last = rules_seq ? 2 : 0;
         h->no_seq3 = false;
         for (int pass = 0; pass < 2; pass++) {
             // the rise-and-fall engine keeps no key blocks: their reset waits for a

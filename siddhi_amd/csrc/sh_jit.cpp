@@ -63,8 +63,9 @@ const int kHalo = env_int("SH_JIT_HALO", 256, 0, 1024);
 // (measured on C2: 4 -> 2.04 ms, 8 -> 2.13 ms, 12 -> 2.42 ms per matcher pass)
 const int kWalkBlock = env_int("SH_BK_WALK", 4, 2, 16);
 // the count walk hands consumers out per lane (SH_BK_DYN=0: every lane of a wave
-// walks its consumer to the wave's longest walk)
-const int kWalkDyn = env_int("SH_BK_DYN", 1, 0, 1);
+// walks its consumer to the wave's longest walk); read where the source is generated,
+// so one process can run both forms
+int walk_dyn() { return env_int("SH_BK_DYN", 1, 0, 1); }
 // the bucketed matcher's launch bound: minimum workgroups per CU the register
 // allocation is sized for (the default 3-KB pass's LDS holds three 512-thread
 // workgroups per CU)
@@ -1233,7 +1234,7 @@ SHB_PROF(1)
     // slow_: some consumer took a partial beyond the mask's SHB_MSTEPS steps (its
     // match-stream values then come from a second walk)
     src += "int slow_ = 0;\n";
-    if (fdom && kWalkDyn) {
+    if (fdom && walk_dyn()) {
         // consumers (chunk events): per-lane work hand-out over each wave's range
         src += "// consumers (chunk events): partials taken per event\n" + walk_count_f_dyn() + "__syncthreads();\n";
     } else {
@@ -1371,6 +1372,8 @@ Entry* compile(const std::string& src) {
         e->err = "hiprtcCreateProgram failed";
         return e;
     }
+    // value semantics ride on this list: subnormals are kept (2^-149 > 0 must hold, as in Java)
+    // and nothing is contracted into an fma (tests/test_gpu_edge_values.py)
     const char* opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
                           "-fno-gpu-flush-denormals-to-zero", "-fhip-fp32-correctly-rounded-divide-sqrt"};
     const hiprtcResult rc = hiprtcCompileProgram(prog, (int)(sizeof(opts) / sizeof(opts[0])), opts);

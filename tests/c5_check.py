@@ -35,7 +35,8 @@ def c5_expected(ts, card, amount, merchant, rules, within_ms=1000, batch=4096, f
         if r in free:
             cand = np.nonzero(sa > a)[0]
         else:
-            lo, hi = np.searchsorted(m_sorted, [m, m + 1])
+            mv = sm.dtype.type(m)  # (not [m, m + 1]: M may be the type's largest value)
+            lo, hi = np.searchsorted(m_sorted, mv, "left"), np.searchsorted(m_sorted, mv, "right")
             cand = np.sort(by_m[lo:hi])
             cand = cand[sa[cand] > a]
         wms = w * within_ms
