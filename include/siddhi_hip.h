@@ -85,7 +85,28 @@ int sh_start(sh_handle* h);
    before it completes: an error the device raises for that batch (state or replay
    capacity, a key id out of range) is returned by the NEXT call into the handle --
    sh_push_batch, sh_drain, sh_pending, sh_advance_time, sh_snapshot or
-   sh_run_device -- and the handle keeps the state from before the failed batch. */
+   sh_run_device -- and the handle keeps the state from before the failed batch.
+
+   Rule sets beyond the general engine's query table (more than 16 queries, each
+   `every e1=S[f1] -> e2=S[f2(e1, e2)] within W`, no aggregators) stream through
+   the rule engine: a call on stream 0 is one send(Event[]) call, of any size, and
+   is staged with each event's own sequence number (an event whose key is -1 is
+   dropped: it takes a number, and it ends the run of same-key events around
+   it, as it does on the general engine's streaming path). The next sh_drain /
+   sh_pending / sh_snapshot -- or sh_push_batch itself once 2^24 events wait --
+   runs one device step over everything staged and appends its matches in the
+   order (run, query, consuming event, opening event); where the steps fall does
+   not show in the rows. Between steps the handle keeps every partial (opening
+   event, rule) that was not consumed and can still be: one whose key's latest
+   event is more than W later is dropped, a key that goes quiet keeps its
+   partials, and each opening event with a live partial is kept once, so the
+   memory held depends on the live partials, not on the events pushed. A step
+   fails with SH_E_UNSUPPORTED when timestamps decrease inside a key (also
+   against the key's last event of an earlier step) or a batch's null mask has
+   a set bit; the staged calls are then dropped, sequence numbers included, and
+   the carried state is what it was before them. Aggregating rule sets of that
+   size are refused here (SH_E_UNSUPPORTED): sh_run_device only. sh_start and
+   sh_advance_time do nothing for such a handle and sh_set_coordinator refuses it. */
 int sh_push_batch(sh_handle* h, const sh_batch* batch);
 
 /* Registers attr.toString() of partition key ids [first_key, first_key + n) as
@@ -127,7 +148,10 @@ const char* sh_last_error(sh_handle* h);
 /* ---- device-resident bulk path (bench / throughput) ----------------------
    Matches on `n` events already resident in HBM for a single-stream app,
    starting from fresh per-key state, writing the ordered match stream to
-   device buffers. Times only device work; the caller owns all buffers. */
+   device buffers. Times only device work; the caller owns all buffers.
+   On a streaming rule-set handle (see sh_push_batch) the call keeps this meaning:
+   it starts from fresh state and neither reads nor changes what the handle
+   carries between sh_push_batch steps. */
 typedef struct sh_device_run {
     int64_t n;                   /* events                                         */
     const int64_t* d_ts;
@@ -204,7 +228,9 @@ int sh_last_kernel_times(sh_handle* h, sh_kernel_times* t);
    their HashMap-order models, per-key aggregates, the playback clock, sequence
    counters and undelivered output, as one opaque versioned image. Pending send()s
    are processed first. buf == NULL or cap < size: *size is set and SH_E_MORE
-   returned. */
+   returned. A streaming rule set's image holds its carried opening events, their
+   live rules, the per-key last timestamps, the sequence and send-call counters
+   and the undelivered output; its fingerprint covers the rule table. */
 int sh_snapshot(sh_handle* h, void* buf, int64_t cap, int64_t* size);
 /* Restore an image into a handle compiled from the same app that has not
    processed events yet (SiddhiAppRuntime.restore(byte[]) / restoreLastRevision,

@@ -696,6 +696,26 @@ static uint64_t fnv1a(const void* p, size_t n, uint64_t h = 1469598103934665603u
 static uint64_t program_fingerprint(const sh_handle* h) {
     uint64_t f = fnv1a(&h->mode, sizeof(h->mode));
     if (h->mode == 1 && h->T) return fnv1a(h->T, sizeof(nf_table), f);
+    if (h->mode == 2) {
+        // a rule set fills no shp_program: the rule table, the index choice, the stream types
+        for (const shr_rule& R : h->r_rules) {
+            f = fnv1a(&R.within, sizeof(R.within), f);
+            f = fnv1a(&R.query, sizeof(R.query), f);
+            f = fnv1a(&R.n_out, sizeof(R.n_out), f);
+            f = fnv1a(R.nt, sizeof(R.nt), f);
+            for (int sl = 0; sl < 2; sl++)
+                for (int t = 0; t < R.nt[sl]; t++) f = fnv1a(&R.t[sl][t], sizeof(shp_term), f);
+            for (int o = 0; o < R.n_out; o++) {
+                f = fnv1a(&R.out_slot[o], 1, f);
+                f = fnv1a(&R.out_attr[o], 1, f);
+            }
+        }
+        f = fnv1a(&h->r_tab.ix_attr, sizeof(h->r_tab.ix_attr), f);
+        const uint8_t part = h->r_partitioned ? 1 : 0;
+        f = fnv1a(&part, 1, f);
+        for (const auto& t : h->stream_types) f = fnv1a(t.data(), t.size() * sizeof(int32_t), f);
+        return f;
+    }
     f = fnv1a(&h->prog, sizeof(h->prog), f);
     for (const auto& t : h->stream_types) f = fnv1a(t.data(), t.size() * sizeof(int32_t), f);
     return f;
@@ -824,6 +844,15 @@ void sh_destroy(sh_handle* h) {
                            &h->n_ctl,
                            &h->r_rec, &h->r_keys, &h->r_g, &h->r_sk, &h->r_sv, &h->r_hist, &h->r_scan, &h->r_run};
         for (DevBuf* b : nbufs) b->release();
+        for (auto& R : h->rc) {
+            DevBuf* rb[] = {&R.ts, &R.key, &R.seq, &R.run, &R.c_off, &R.c_rule};
+            for (DevBuf* b : rb) b->release();
+            for (auto& c : R.col) c.release();
+        }
+        h->rc_klast.release();
+        h->rc_ws.release();
+        h->rc_oq.release();
+        h->rc_ots.release();
         for (auto& st : h->stores) {
             for (auto& c : st.cols) c.release();
             for (auto& c : st.nuls) c.release();
@@ -837,6 +866,11 @@ void sh_destroy(sh_handle* h) {
 }
 
 
+// a streaming rule set's staged events at which sh_push_batch runs the step itself:
+// bounds the host staging when nobody drains, and keeps carried rows (below 2^31 -
+// 2^24 in any state a step accepts) plus staged rows below 2^31
+static const int64_t kRuleStageCap = (int64_t)1 << 24;
+
 static int push_impl(sh_handle* h, const sh_batch* b, const uint32_t* index, int64_t call_n, int64_t call_last) {
     HpScope hp_(h, 0);
     if (h && h->poisoned) return fail(h, SH_E_INVALID_ARG, "handle unusable after a failed restore");
@@ -844,9 +878,19 @@ static int push_impl(sh_handle* h, const sh_batch* b, const uint32_t* index, int
     if (!h->has_device) return fail(h, SH_E_NO_DEVICE, "no HIP device: the matcher has no CPU fallback");
     if (b->stream < 0 || b->stream >= h->app.n_streams) return fail(h, SH_E_INVALID_ARG, "bad stream index");
     if (b->on_device) return fail(h, SH_E_UNSUPPORTED, "device batches go through sh_run_device");
-    if (h->mode == 2)
-        return fail(h, SH_E_UNSUPPORTED, "rule sets larger than the general engine's query table run through "
-                                         "sh_run_device only");
+    if (h->mode == 2) {
+        // one send(Event[]) call of a streaming rule set: staged; the device step runs
+        // at the next flush, or here once kRuleStageCap events wait
+        if (h->r_aggp)
+            return fail(h, SH_E_UNSUPPORTED, "aggregating rule sets larger than the general engine's query table "
+                                             "run through sh_run_device only (no carried aggregates)");
+        if (index) return fail(h, SH_E_INVALID_ARG, "sh_push_batch_part needs sh_set_coordinator first");
+        if (b->stream != 0) return fail(h, SH_E_INVALID_ARG, "bad stream index");
+        if (b->n <= 0) return SH_OK;
+        const int src = rules_stage(h, b);
+        if (src) return src;
+        return (int64_t)h->rq_ts.size() >= kRuleStageCap ? flush(h) : SH_OK;
+    }
     if (h->coord_on && !index)
         return fail(h, SH_E_INVALID_ARG, "a key-sharded handle takes its events through sh_push_batch_part");
     if (index) {
@@ -1170,6 +1214,10 @@ int flush(sh_handle* h) {
     if (h->mode == 1) {  // the general engine processes each send() at once
         const int src = nf_settle(h);  // (a push's launch may still be pending)
         return src ? src : nf_app_pull(h);
+    }
+    if (h->mode == 2) {
+        if (!h->has_device) return SH_OK;  // (nothing can have been pushed)
+        return rules_step(h);
     }
     const int64_t n = (int64_t)h->st_ts.size();
     if (n == 0) return SH_OK;
@@ -1737,6 +1785,15 @@ int shx_seq3_status(sh_handle* h) { return h ? (h->s3b_last ? 2 : h->seq3_last) 
 int shx_agg_status(sh_handle* h) { return h ? h->agg_last : 0; }
 
 int shx_rules_status(sh_handle* h) { return h ? h->rs_last : 0; }
+
+// the carried state of a streaming rule set after its last step: live partials
+// (opening event, rule) and the distinct opening events kept; returns the steps run
+int shx_rules_carry(sh_handle* h, int64_t* partials, int64_t* rows) {
+    if (!h) return 0;
+    if (partials) *partials = h->rc_pairs;
+    if (rows) *rows = h->rc_rows;
+    return (int)std::min<int64_t>(h->rc_steps, 0x7FFFFFFF);
+}
 
 // SH_HOST_PROF phase clocks of a streaming handle (ms and counts, SH_HP_N phases)
 int shx_host_profile(sh_handle* h, double* ms, int64_t* n, int cap) {

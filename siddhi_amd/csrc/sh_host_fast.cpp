@@ -1,5 +1,6 @@
 // sh_host_fast.cpp -- drivers of the fast batch engines behind sh_run_device:
-// the rule engine (sh_rules.hip), the tile-local bucketed window engine and the
+// the rule engine (sh_rules.hip; also its streaming step behind sh_push_batch,
+// rules_stage / rules_step), the tile-local bucketed window engine and the
 // sequence bucket-carry engine (sh_bucket.hip + shb_match), the aggregate post-pass
 // (sh_agg.hip), and the key-segment helpers they share.
 #include "sh_host_int.h"
@@ -184,7 +185,7 @@ static int rules_order_place(sh_handle* h, sh_device_run* run, int64_t m, const 
         }
     }
     if (shr_place(dT, order, m, rec_p, rec_q, rec_r, perm, sts, dC, 0, std::max(1, h->n_out), run->d_out_seq,
-                  run->d_out_query, nullptr, run->d_out_values, st, sts32, tlo))
+                  run->d_out_query, h->step_ots, run->d_out_values, st, sts32, tlo, h->step_seqs))
         return fail(h, SH_E_HIP, "rule placement launch failed");
     return SH_OK;
 }
@@ -435,6 +436,291 @@ int run_rules(sh_handle* h, sh_device_run* run) {
         hipEventRecord(h->ev[2], st);
     }
     return rules_finish(h, run, m, nkeys);
+}
+
+// ---- streaming rule sets (mode 2): sh_push_batch stages, flush runs one step
+//
+// One send(Event[]) call of a rule set beyond the general engine's table. The keyed
+// events are appended to the host staging with their own sequence numbers (a
+// null-key event is dropped but takes a number) and their PartitionStreamReceiver
+// run: the consecutive same-key events of the call, or the whole call when
+// unpartitioned. A dropped event ends the run around it, as it does for the general
+// engine's streaming path (sh_nfa.hip joins(): a run's events are adjacent in the
+// call) and for the oracle, so a rule set orders its rows the same on either side of
+// the 16-query table. (The bulk path's k_run_flags skips such an event inside a run.)
+int rules_stage(sh_handle* h, const sh_batch* b) {
+    const auto& types = h->stream_types[0];
+    const int na = (int)types.size();
+    if (na > 7) return fail(h, SH_E_UNSUPPORTED, "rule engine: at most 7 attributes per stream");
+    if (h->rq_ts.empty() && !h->rq_nullbit) h->rq_call0 = h->rq_call;
+    if (b->nulls)
+        for (int a = 0; a < na && !h->rq_nullbit; a++)
+            if (b->nulls[a])
+                for (int64_t i = 0; i < b->n; i++)
+                    if (b->nulls[a][i]) {
+                        h->rq_nullbit = true;
+                        break;
+                    }
+    bool any = false, dropped = false;
+    int32_t prev = -1;
+    const size_t at = h->rq_ts.size();
+    for (int64_t i = 0; i < b->n; i++) {
+        const int32_t k = h->partitioned ? (b->keys ? b->keys[i] : -1) : 0;
+        if (k < 0) {
+            dropped = true;
+            prev = -1;  // the next keyed event starts a run
+            continue;
+        }
+        if (!any || (h->partitioned && k != prev)) h->rq_run_next++;
+        any = true;
+        prev = k;
+        h->rq_ts.push_back(b->ts[i]);
+        h->rq_key.push_back(k);
+        h->rq_seq.push_back(h->seq_next + (uint64_t)i);
+        h->rq_run.push_back(h->rq_run_next);
+        if (k + 1 > h->max_key) h->max_key = k + 1;
+    }
+    for (int a = 0; a < na; a++) {
+        const size_t w = (size_t)type_width(types[a]);
+        const uint8_t* src = (const uint8_t*)b->cols[a];
+        if (!dropped) {  // the whole column at once
+            h->rq_col[a].insert(h->rq_col[a].end(), src, src + (size_t)b->n * w);
+            continue;
+        }
+        for (size_t j = at; j < h->rq_ts.size(); j++) {
+            const size_t i = (size_t)(h->rq_seq[j] - h->seq_next);
+            h->rq_col[a].insert(h->rq_col[a].end(), src + i * w, src + (i + 1) * w);
+        }
+    }
+    h->seq_next += (uint64_t)b->n;
+    h->rq_call++;
+    return SH_OK;
+}
+
+// the staged calls are dropped: a refused step leaves the handle where it was
+// before them (counters included), with the carried state untouched
+static int rules_step_fail(sh_handle* h, int code, const char* msg) {
+    h->rq_ts.clear();
+    h->rq_key.clear();
+    h->rq_seq.clear();
+    h->rq_run.clear();
+    for (auto& c : h->rq_col) c.clear();
+    h->rq_run_next = 0;
+    h->rq_nullbit = false;
+    h->seq_next = h->seq_staged0;
+    h->rq_call = h->rq_call0;
+    h->step_seqs = nullptr;
+    h->step_ots = nullptr;
+    return fail(h, code, msg);
+}
+
+// One device step over everything staged: the key-segment scans run over the
+// carried opening events followed by the staged events (shr_carry), the records
+// are ordered and placed as in run_rules and appended to the host output queue,
+// and the survivors become the next carried state in the other store. The sparse
+// path is not taken: it keeps no survivors.
+int rules_step(sh_handle* h) {
+    if (h->rq_ts.empty() && !h->rq_nullbit) {
+        h->seq_staged0 = h->seq_next;  // (calls of null-key events only)
+        h->rq_call0 = h->rq_call;
+        return SH_OK;
+    }
+    if (h->rq_nullbit)
+        return rules_step_fail(h, SH_E_UNSUPPORTED, "rule engine: null attribute values are not supported");
+    h->stream = h->own_stream;
+    hipStream_t st = h->stream;
+    const auto& types = h->stream_types[0];
+    const int na = (int)types.size();
+    const int64_t ns = (int64_t)h->rq_ts.size(), nc = h->rc_rows, n = nc + ns;
+    if (n >= 0x7FFFFFFFll) return rules_step_fail(h, SH_E_UNSUPPORTED, "rule engine: carried plus staged rows >= 2^31");
+    const bool sorted = h->r_partitioned;
+    const int32_t nkeys = sorted ? std::max(1, h->max_key) : 1;
+    sh_handle::RuleStore& A = h->rc[h->rc_cur];
+    sh_handle::RuleStore& Bn = h->rc[1 - h->rc_cur];
+    int oom = A.ts.ensure((size_t)n * 8) | A.key.ensure((size_t)n * 4) | A.seq.ensure((size_t)n * 8) |
+              A.run.ensure((size_t)n * 4) | A.c_off.ensure(((size_t)nc + 1) * 4) | A.c_rule.ensure(4);
+    for (int a = 0; a < na; a++) oom |= A.col[a].ensure((size_t)n * type_width(types[a]));
+    if (nkeys > h->rc_nkeys) {
+        const int32_t nk = std::max(nkeys, h->rc_nkeys * 2);
+        oom |= h->rc_klast.ensure((size_t)nk * 8);
+        if (!oom && shr_fill_i64(h->rc_klast.as<int64_t>() + h->rc_nkeys, nk - h->rc_nkeys, INT64_MIN, st)) oom = 1;
+        if (!oom) h->rc_nkeys = nk;
+    }
+    const int64_t nb = shr_carry_blocks(n);
+    // workspace: scnt [n + 1], soff [n + 1], lid [n], blk [nb + 1], blk_off [nb + 1]
+    oom |= h->rc_ws.ensure_fresh(((size_t)3 * n + 2 * nb + 8) * 4);
+    if (oom || ensure_ws(h, std::max(n + 1, nb + 1)) || h->v_flag.ensure_fresh(64))
+        return rules_step_fail(h, SH_E_OOM, "rule step workspace");
+    if (nc == 0) hipMemsetAsync(A.c_off.p, 0, 4, st);
+    hipMemsetAsync(A.run.p, 0, (size_t)nc * 4, st);  // carried rows: run 0, never a consumer's
+    hipMemcpyAsync(A.ts.as<int64_t>() + nc, h->rq_ts.data(), (size_t)ns * 8, hipMemcpyHostToDevice, st);
+    hipMemcpyAsync(A.key.as<int32_t>() + nc, h->rq_key.data(), (size_t)ns * 4, hipMemcpyHostToDevice, st);
+    hipMemcpyAsync(A.seq.as<uint64_t>() + nc, h->rq_seq.data(), (size_t)ns * 8, hipMemcpyHostToDevice, st);
+    hipMemcpyAsync(A.run.as<uint32_t>() + nc, h->rq_run.data(), (size_t)ns * 4, hipMemcpyHostToDevice, st);
+    const void* colp[8] = {nullptr};
+    for (int a = 0; a < na; a++) {
+        const size_t w = (size_t)type_width(types[a]);
+        hipMemcpyAsync(A.col[a].as<uint8_t>() + (size_t)nc * w, h->rq_col[a].data(), (size_t)ns * w,
+                       hipMemcpyHostToDevice, st);
+        colp[a] = A.col[a].p;
+    }
+    h->times = sh_kernel_times{};
+    sh_device_run R;
+    memset(&R, 0, sizeof(R));
+    R.n = n;
+    R.d_ts = A.ts.as<int64_t>();
+    R.d_keys = A.key.as<int32_t>();
+    R.n_keys = nkeys;
+    R.d_cols = colp;
+    R.d_run = A.run.as<uint32_t>();
+    shd_batch B;
+    memset(&B, 0, sizeof(B));
+    B.ts = R.d_ts;
+    B.keys = sorted ? R.d_keys : nullptr;
+    B.n = n;
+    shd_payload carry;
+    void* mid[8] = {nullptr};
+    int alias = -1;
+    hipEventRecord(h->ev[0], st);
+    if (sorted && carry_setup(h, &R, &carry, mid, &alias, false, true))
+        return rules_step_fail(h, SH_E_OOM, "rule step workspace");
+    shd_segment_ws ws = seg_ws(h, n);
+    const uint32_t* perm = nullptr;
+    const uint32_t* skeys = nullptr;
+    if (shd_segment_payload(&B, nkeys, &ws, st, &perm, &skeys, sorted ? &carry : nullptr, mid, 0, 0))
+        return rules_step_fail(h, SH_E_HIP, "segment launch failed");
+    hipEventRecord(h->ev[1], st);
+    const int64_t* sts = sorted ? h->v_sts.as<int64_t>() : R.d_ts;
+    shd_cols sc;
+    memset(&sc, 0, sizeof(sc));
+    for (int a = 0; a < na; a++) sc.col[0][a] = sorted ? (const void*)h->v_scol[a].p : colp[a];
+    if (alias >= 0) sc.col[0][alias] = skeys;
+    hipMemcpyAsync(h->d_cols_desc.p, &sc, sizeof(sc), hipMemcpyHostToDevice, st);
+    const shd_cols* dC = h->d_cols_desc.as<shd_cols>();
+    const shr_table* dT = h->rd_tab.as<shr_table>();
+    const uint32_t sentinel = sorted ? (uint32_t)nkeys : 0xFFFFFFFFu;
+    uint32_t* cnt = h->w_cnt.as<uint32_t>();
+    uint32_t* off = h->w_off.as<uint32_t>();
+    uint32_t* scnt = h->rc_ws.as<uint32_t>();
+    uint32_t* soff = scnt + (n + 1);
+    uint32_t* lid = soff + (n + 1);
+    uint32_t* blk = lid + n;
+    uint32_t* blk_off = blk + (nb + 1);
+    shr_carry K;
+    memset(&K, 0, sizeof(K));
+    K.nc = (uint32_t)nc;
+    K.perm = perm;
+    K.c_off = A.c_off.as<uint32_t>();
+    K.c_rule = A.c_rule.as<uint32_t>();
+    K.klast = h->rc_klast.as<int64_t>();
+    K.scnt = scnt;
+    const uint8_t* img = h->r_img.bytes ? h->rd_img.as<uint8_t>() : nullptr;
+    hipMemsetAsync(h->v_flag.p, 0, 8, st);
+    hipMemsetAsync(cnt, 0, (size_t)n * 4, st);
+    hipMemsetAsync(scnt, 0, ((size_t)n + 1) * 4, st);
+    hipMemsetAsync(blk + nb, 0, 4, st);
+    if (shr_count(dT, sts, skeys, n, sentinel, dC, cnt, h->v_flag.as<int32_t>(), st, img, &h->r_img, nullptr, 0, &K) ||
+        shd_exclusive_scan(cnt, off, n, h->w_scan.as<uint32_t>(), st) ||
+        shd_exclusive_scan(scnt, soff, n + 1, h->w_scan.as<uint32_t>(), st) || shr_carry_ids(scnt, n, lid, blk, st) ||
+        shd_exclusive_scan(blk, blk_off, nb + 1, h->w_scan.as<uint32_t>(), st))
+        return rules_step_fail(h, SH_E_HIP, "rule scan launch failed");
+    uint32_t lo = 0, lc = 0, npairs = 0, nrows = 0;
+    int32_t flag = 0;
+    hipMemcpyAsync(&lo, off + (n - 1), 4, hipMemcpyDeviceToHost, st);
+    hipMemcpyAsync(&lc, cnt + (n - 1), 4, hipMemcpyDeviceToHost, st);
+    hipMemcpyAsync(&npairs, soff + n, 4, hipMemcpyDeviceToHost, st);
+    hipMemcpyAsync(&nrows, blk_off + nb, 4, hipMemcpyDeviceToHost, st);
+    hipMemcpyAsync(&flag, h->v_flag.p, 4, hipMemcpyDeviceToHost, st);
+    if (hipStreamSynchronize(st) != hipSuccess) return rules_step_fail(h, SH_E_HIP, "device error in the rule scan");
+    if (flag) return rules_step_fail(h, SH_E_UNSUPPORTED, "rule engine: timestamps decrease inside a key");
+    const int64_t m = (int64_t)lo + lc;
+    // the next carried state, beside the current one
+    oom = Bn.ts.ensure_fresh(std::max<size_t>(nrows, 1) * 8) | Bn.key.ensure_fresh(std::max<size_t>(nrows, 1) * 4) |
+          Bn.seq.ensure_fresh(std::max<size_t>(nrows, 1) * 8) | Bn.c_off.ensure_fresh(((size_t)nrows + 1) * 4) |
+          Bn.c_rule.ensure_fresh(std::max<size_t>(npairs, 1) * 4);
+    void* cdst[8] = {nullptr};
+    int32_t cw[8] = {0};
+    for (int a = 0; a < na; a++) {
+        cw[a] = type_width(types[a]);
+        oom |= Bn.col[a].ensure_fresh(std::max<size_t>(nrows, 1) * cw[a]);
+        cdst[a] = Bn.col[a].p;
+    }
+    if (oom || h->r_rec.ensure_fresh((size_t)std::max<int64_t>(m, 1) * 12))
+        return rules_step_fail(h, SH_E_OOM, "rule step state");
+    K.soff = soff;
+    K.s_rule = Bn.c_rule.as<uint32_t>();
+    uint32_t* rec_p = h->r_rec.as<uint32_t>();
+    uint32_t* rec_q = rec_p + m;
+    uint32_t* rec_r = rec_q + m;
+    if ((m > 0 || npairs > 0) &&
+        shr_write(dT, sts, skeys, n, sentinel, dC, cnt, off, rec_p, rec_q, rec_r, st, img, &h->r_img, nullptr, 0, &K))
+        return rules_step_fail(h, SH_E_HIP, "rule write launch failed");
+    const int no = std::max(1, h->n_out);
+    if (m > 0) {
+        if (h->w_oseq.ensure_fresh((size_t)m * 8) || h->rc_ots.ensure_fresh((size_t)m * 8) ||
+            h->rc_oq.ensure_fresh((size_t)m * 4) || h->w_ovals.ensure_fresh((size_t)m * no * 8))
+            return rules_step_fail(h, SH_E_OOM, "output buffers");
+        R.d_out_seq = h->w_oseq.as<uint64_t>();
+        R.d_out_query = h->rc_oq.as<int32_t>();
+        R.d_out_values = h->w_ovals.as<int64_t>();
+        R.out_capacity = m;
+        h->step_seqs = A.seq.as<uint64_t>();
+        h->step_ots = h->rc_ots.as<int64_t>();
+        // (runs from the staged events' run ids, for unpartitioned sets too)
+        const int prc = rules_order_place(h, &R, m, rec_p, rec_q, rec_r, perm, sts, dC, nullptr, 0, true, false);
+        h->step_seqs = nullptr;
+        h->step_ots = nullptr;
+        if (prc) return rules_step_fail(h, prc, h->err.c_str());
+    } else {
+        hipEventRecord(h->ev[2], st);
+    }
+    if (shr_carry_rows(scnt, soff, n, lid, blk_off, A.ts.as<int64_t>(), A.key.as<int32_t>(), A.seq.as<uint64_t>(),
+                       Bn.ts.as<int64_t>(), Bn.key.as<int32_t>(), Bn.seq.as<uint64_t>(), Bn.c_off.as<uint32_t>(), na,
+                       colp, cdst, cw, st))
+        return rules_step_fail(h, SH_E_HIP, "rule carry launch failed");
+    // rows into the host output queue; the per-key last timestamps move last, when
+    // nothing can refuse the step any more
+    const size_t base = h->o_seq.size();
+    h->o_query.resize(base + m);
+    h->o_seq.resize(base + m);
+    h->o_ts.resize(base + m);
+    h->o_vals.resize((base + m) * h->n_out);
+    h->o_nulls.resize((base + m) * h->n_out, 0);
+    if (m > 0) {
+        hipMemcpyAsync(h->o_query.data() + base, h->rc_oq.p, (size_t)m * 4, hipMemcpyDeviceToHost, st);
+        hipMemcpyAsync(h->o_seq.data() + base, h->w_oseq.p, (size_t)m * 8, hipMemcpyDeviceToHost, st);
+        hipMemcpyAsync(h->o_ts.data() + base, h->rc_ots.p, (size_t)m * 8, hipMemcpyDeviceToHost, st);
+        if (h->n_out)
+            hipMemcpyAsync(h->o_vals.data() + base * h->n_out, h->w_ovals.p, (size_t)m * h->n_out * 8,
+                           hipMemcpyDeviceToHost, st);
+    }
+    if (shr_klast_update(sts, skeys, perm, n, (uint32_t)nc, h->rc_klast.as<int64_t>(), st) ||
+        (hipEventRecord(h->ev[3], st), hipStreamSynchronize(st)) != hipSuccess) {
+        h->o_query.resize(base);
+        h->o_seq.resize(base);
+        h->o_ts.resize(base);
+        h->o_vals.resize(base * h->n_out);
+        h->o_nulls.resize(base * h->n_out);
+        return rules_step_fail(h, SH_E_HIP, "device error in the rule step");
+    }
+    hipEventElapsedTime(&h->times.segment_ms, h->ev[0], h->ev[1]);
+    hipEventElapsedTime(&h->times.advance_ms, h->ev[1], h->ev[2]);
+    hipEventElapsedTime(&h->times.emit_ms, h->ev[2], h->ev[3]);
+    hipEventElapsedTime(&h->times.total_ms, h->ev[0], h->ev[3]);
+    h->rc_cur = 1 - h->rc_cur;
+    h->rc_rows = nrows;
+    h->rc_pairs = npairs;
+    h->rc_steps++;
+    h->rs_last = 0;
+    h->rq_ts.clear();
+    h->rq_key.clear();
+    h->rq_seq.clear();
+    h->rq_run.clear();
+    for (auto& c : h->rq_col) c.clear();
+    h->rq_run_next = 0;
+    h->seq_staged0 = h->seq_next;
+    h->rq_call0 = h->rq_call;
+    return SH_OK;
 }
 
 // bucketed window engine (sh_bucket.hip): partitioned window programs with a

@@ -324,6 +324,33 @@ struct sh_handle {
     // the keys' lists (opening event, rule, consuming event, expiry), counters
     DevBuf rs_pr, rs_key, rs_list, rs_ctl, rs_live;
     int rs_last = 0;  // 1: the last rule run took the sparse-partial path
+    // ---- streaming rule sets (mode 2: sh_push_batch / flush -> rules_step, sh_host_fast.cpp)
+    // staged send() calls: the keyed events' timestamp, key, own sequence number,
+    // PartitionStreamReceiver run (1.. inside the step) and attribute columns
+    std::vector<int64_t> rq_ts;
+    std::vector<int32_t> rq_key;
+    std::vector<uint64_t> rq_seq;
+    std::vector<uint32_t> rq_run;
+    std::vector<uint8_t> rq_col[8];
+    uint32_t rq_run_next = 0;
+    bool rq_nullbit = false;             // a staged call carried a set null-mask bit: the step refuses
+    uint64_t rq_call = 0, rq_call0 = 0;  // send-call counter (next call's id; at the first staged call)
+    // carried state: the opening events that still hold a live partial, once each in
+    // arrival order, and per row its live rules (CSR); two stores, the step reads
+    // rc[rc_cur] (carried rows, then the staged events appended behind them) and
+    // builds rc[1 - rc_cur], swapped in when the step succeeded
+    struct RuleStore {
+        DevBuf ts, key, seq, run, col[8], c_off, c_rule;
+    };
+    RuleStore rc[2];
+    int rc_cur = 0;
+    int64_t rc_rows = 0, rc_pairs = 0;   // carried rows / partials after the last step
+    int64_t rc_steps = 0;
+    DevBuf rc_klast;                     // per key: timestamp of its last event so far (INT64_MIN: none)
+    int32_t rc_nkeys = 0;
+    DevBuf rc_ws, rc_oq, rc_ots;         // step workspace; placed query ids and timestamps
+    const uint64_t* step_seqs = nullptr; // rules_order_place: the events' own sequence numbers (a step)
+    int64_t* step_ots = nullptr;         // ... and where the rows' timestamps go
     // ---- bucketed window engine (sh_bucket.hip + shb_match): 0 untried, 1 loaded, <0 unavailable
     int bk_state = 0;
     int32_t part_attr0 = -1;  // stream-0 attribute keying query 0's partition
@@ -416,6 +443,8 @@ int rows_for_cols(sh_handle* h, sh_device_run* run);
 void direct_layout(sh_handle* h, sh_device_run* run, const int32_t* widths, int n_out, shb_cols* OC);
 int run_bucket(sh_handle* h, sh_device_run* run, int32_t nkeys, bool force_carry = false);
 int run_rules(sh_handle* h, sh_device_run* run);
+int rules_stage(sh_handle* h, const sh_batch* b);
+int rules_step(sh_handle* h);
 int run_s3b(sh_handle* h, sh_device_run* run, int32_t nkeys);
 shd_segment_ws seg_ws(sh_handle* h, int64_t n);
 int tile_shift_for(int64_t n, int32_t nkeys);
@@ -428,6 +457,7 @@ int shx_bucket_status(sh_handle* h);
 int shx_seq3_status(sh_handle* h);
 int shx_agg_status(sh_handle* h);
 int shx_rules_status(sh_handle* h);
+int shx_rules_carry(sh_handle* h, int64_t* partials, int64_t* rows);
 int shx_host_profile(sh_handle* h, double* ms, int64_t* n, int cap);
 int shx_seq3_shape(sh_handle* h);
 int shx_bucket_compile(sh_handle* h, char* buf, int64_t len);

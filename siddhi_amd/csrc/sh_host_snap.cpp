@@ -151,7 +151,8 @@ void get_jmap(SnapR& r, ShJMap& M) {
 }  // namespace
 
 static int snapshot_image(sh_handle* h, SnapW& w) {
-    if (h->mode == 2) return fail(h, SH_E_UNSUPPORTED, "snapshot: rule sets run through sh_run_device only");
+    if (h->mode == 2 && h->r_aggp)
+        return fail(h, SH_E_UNSUPPORTED, "snapshot: aggregating rule sets run through sh_run_device only");
     int rc = flush(h);  // pending send()s are processed first
     if (rc) return rc;
     if (h->has_device && hipStreamSynchronize(h->stream) != hipSuccess) return fail(h, SH_E_HIP, "snapshot sync");
@@ -188,7 +189,23 @@ static int snapshot_image(sh_handle* h, SnapW& w) {
             w.dev(st.nuls[a], st.has_nul[a] ? (size_t)st.rows : 0);
         }
     }
-    if (h->mode == 0) {
+    if (h->mode == 2) {
+        // a streaming rule set: the carried opening events, their live rules (CSR), the
+        // per-key last timestamps and the send-call counter
+        const auto& A = h->rc[h->rc_cur];
+        const size_t nr = (size_t)h->rc_rows, np = (size_t)h->rc_pairs;
+        w.put(h->rc_rows);
+        w.put(h->rc_pairs);
+        w.put(h->rc_nkeys);
+        w.put(h->rq_call);
+        w.dev(A.ts, nr * 8);
+        w.dev(A.key, nr * 4);
+        w.dev(A.seq, nr * 8);
+        for (size_t a = 0; a < h->stream_types[0].size(); a++) w.dev(A.col[a], nr * type_width(h->stream_types[0][a]));
+        w.dev(A.c_off, nr ? (nr + 1) * 4 : 0);
+        w.dev(A.c_rule, np * 4);
+        w.dev(h->rc_klast, (size_t)h->rc_nkeys * 8);
+    } else if (h->mode == 0) {
         w.put(h->lay);
         w.put(h->nkeys_alloc);
         w.dev(h->d_kstate, (size_t)h->nkeys_alloc * h->lay.key_bytes);
@@ -256,6 +273,9 @@ int sh_restore(sh_handle* h, const void* buf, int64_t size) {
     if (!h->has_device) return fail(h, SH_E_NO_DEVICE, "no HIP device: the matcher has no CPU fallback");
     for (auto& st : h->stores)
         if (st.rows) return fail(h, SH_E_INVALID_ARG, "restore: the handle has processed events already");
+    // (a rule set's column store is cut back after every step: its counters tell)
+    if (h->mode == 2 && (h->seq_next || h->rc_rows || h->rc_steps))
+        return fail(h, SH_E_INVALID_ARG, "restore: the handle has processed events already");
     // the image is applied as it is parsed: keep the handle's own (fresh) image
     // and put it back when the new one turns out damaged, so a failed restore
     // leaves the handle as it was
@@ -313,7 +333,31 @@ static int restore_image(sh_handle* h, const void* buf, int64_t size) {
             r.dev(st.nuls[a]);
         }
     }
-    if (h->mode == 0 && !r.bad) {
+    if (h->mode == 2 && !r.bad) {
+        auto& A = h->rc[h->rc_cur];
+        h->rq_ts.clear();
+        h->rq_key.clear();
+        h->rq_seq.clear();
+        h->rq_run.clear();
+        for (auto& c : h->rq_col) c.clear();
+        h->rq_run_next = 0;
+        h->rq_nullbit = false;
+        h->rc_rows = r.get<int64_t>();
+        h->rc_pairs = r.get<int64_t>();
+        h->rc_nkeys = r.get<int32_t>();
+        h->rq_call = h->rq_call0 = r.get<uint64_t>();
+        const uint64_t nr = (uint64_t)h->rc_rows, np = (uint64_t)h->rc_pairs;
+        if (h->rc_rows < 0 || h->rc_pairs < 0 || h->rc_nkeys < 0) r.bad = true;
+        if (!r.bad && r.dev(A.ts) != nr * 8) r.bad = true;
+        if (!r.bad && r.dev(A.key) != nr * 4) r.bad = true;
+        if (!r.bad && r.dev(A.seq) != nr * 8) r.bad = true;
+        for (size_t a = 0; a < h->stream_types[0].size() && !r.bad; a++)
+            if (r.dev(A.col[a]) != nr * type_width(h->stream_types[0][a])) r.bad = true;
+        if (!r.bad && r.dev(A.c_off) != (nr ? (nr + 1) * 4 : 0)) r.bad = true;
+        if (!r.bad && r.dev(A.c_rule) != np * 4) r.bad = true;
+        if (!r.bad && r.dev(h->rc_klast) != (uint64_t)h->rc_nkeys * 8) r.bad = true;
+        if (r.bad) h->rc_rows = h->rc_pairs = h->rc_nkeys = 0;
+    } else if (h->mode == 0 && !r.bad) {
         h->lay = r.get<shp_layout>();
         h->nkeys_alloc = r.get<int32_t>();
         r.dev(h->d_kstate);

@@ -54,6 +54,23 @@ struct shr_img {
 };
 #define SHR_IMG_MAX (144 * 1024)
 
+// a streaming step (sh_host_fast.cpp rules_step): the scans run over the carried
+// opening events, arrival indices [0, nc), followed by the staged events [nc, n).
+// A carried row opens only the rules it still holds a partial of and never
+// consumes; the scans also find the step's survivors -- the partials (p, r) opened
+// or carried, not consumed, and not past W_r at their key's last timestamp.
+struct shr_carry {
+    uint32_t nc;                        // carried rows
+    uint32_t pad;
+    const uint32_t* perm;               // key-segment position -> arrival index (NULL: the identity)
+    const uint32_t* c_off;              // [nc + 1] carried row i holds partials of c_rule[c_off[i] .. c_off[i + 1])
+    const uint32_t* c_rule;             // rule ids, ascending per row
+    const int64_t* klast;               // per key: the last timestamp of the earlier steps (INT64_MIN: none)
+    uint32_t* scnt;                     // [n] survivors per arrival index (count pass: out, write pass: in)
+    const uint32_t* soff;               // [n + 1] exclusive scan of scnt (write pass)
+    uint32_t* s_rule;                   // the survivors' rule ids, from soff[arrival index] on, ascending per row
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -62,12 +79,13 @@ extern "C" {
 // sts32 (optional): the sorted timestamps as 32-bit offsets from tbase (sts unused)
 int shr_count(const shr_table* dT, const int64_t* sts, const uint32_t* skeys, int64_t n, uint32_t sentinel,
               const shd_cols* dC, uint32_t* cnt, int32_t* flag, void* stream, const uint8_t* img = nullptr,
-              const shr_img* I = nullptr, const uint32_t* sts32 = nullptr, int64_t tbase = 0);
+              const shr_img* I = nullptr, const uint32_t* sts32 = nullptr, int64_t tbase = 0,
+              const shr_carry* K = nullptr);
 // the same scan, writing (opening, consuming, rule) records at off[p]
 int shr_write(const shr_table* dT, const int64_t* sts, const uint32_t* skeys, int64_t n, uint32_t sentinel,
               const shd_cols* dC, const uint32_t* cnt, const uint32_t* off, uint32_t* rec_p, uint32_t* rec_q,
               uint32_t* rec_r, void* stream, const uint8_t* img = nullptr, const shr_img* I = nullptr,
-              const uint32_t* sts32 = nullptr, int64_t tbase = 0);
+              const uint32_t* sts32 = nullptr, int64_t tbase = 0, const shr_carry* K = nullptr);
 // PartitionStreamReceiver runs of an arrival-order key array: flags[i] (run
 // start), rid[i] (exclusive scan of flags), rfirst[run] (first arrival index);
 // run_ids (may be NULL): the caller's run of every event (sh_device_run.d_run)
@@ -89,11 +107,30 @@ int shr_order_ties(uint32_t* order, int64_t m, const uint32_t* k0, const uint32_
                    const uint32_t* rec_p, void* stream);
 // gk[i] = key[order[i]], gv[i] = order[i] (order NULL: identity)
 int shr_gather(const uint32_t* key, const uint32_t* order, int64_t m, uint32_t* gk, uint32_t* gv, void* stream);
-// ordered output rows from the sorted record order
+// ordered output rows from the sorted record order (seqs: the events' own sequence
+// numbers by arrival index, instead of seq_base + arrival index)
 int shr_place(const shr_table* dT, const uint32_t* order, int64_t m, const uint32_t* rec_p, const uint32_t* rec_q,
               const uint32_t* rec_r, const uint32_t* perm, const int64_t* sts, const shd_cols* dC, uint64_t seq_base,
               int n_out, uint64_t* out_seq, int32_t* out_query, int64_t* out_ts, int64_t* out_vals, void* stream,
-              const uint32_t* sts32 = nullptr, int64_t tbase = 0);
+              const uint32_t* sts32 = nullptr, int64_t tbase = 0, const uint64_t* seqs = nullptr);
+// a streaming step's next carried state (sh_rules.hip, "carried state"):
+// shr_carry_ids: lid[i] = rows with survivors before row i inside its workgroup of
+// shr_carry_blocks(n) workgroups, blk[b] = such rows of workgroup b;
+// shr_carry_rows: blk_off = the exclusive scan of blk over shr_carry_blocks(n) + 1
+// entries (the last: the row count); every row with scnt[i] > 0 is copied to row
+// blk_off[b] + lid[i] of n_ts / n_key / n_seq / the n_cols columns (width 8, 4 or 1),
+// n_off[that row] = soff[i] and n_off[row count] = soff[n]
+int64_t shr_carry_blocks(int64_t n);
+int shr_carry_ids(const uint32_t* scnt, int64_t n, uint32_t* lid, uint32_t* blk, void* stream);
+int shr_carry_rows(const uint32_t* scnt, const uint32_t* soff, int64_t n, const uint32_t* lid, const uint32_t* blk_off,
+                   const int64_t* ts, const int32_t* key, const uint64_t* seq, int64_t* n_ts, int32_t* n_key,
+                   uint64_t* n_seq, uint32_t* n_off, int n_cols, const void* const* src, void* const* dst,
+                   const int32_t* width, void* stream);
+// klast[key] = the timestamp of the key's last staged row (arrival index >= nc) in
+// key-segment order (skeys / perm NULL: one key in arrival order)
+int shr_klast_update(const int64_t* sts, const uint32_t* skeys, const uint32_t* perm, int64_t n, uint32_t nc,
+                     int64_t* klast, void* stream);
+int shr_fill_i64(int64_t* a, int64_t n, int64_t v, void* stream);
 // sparse partials over arrival order (no key segment; sh_rules.hip): pre[2] (or
 // NULL) the attributes f1 reads most on the event's row, loaded with the event; the partials
 // (p, r, key) of every event into pr_* (count in *ctr, at most cap written), and

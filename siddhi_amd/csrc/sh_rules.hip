@@ -26,6 +26,11 @@
 // (matches per opening event) -> exclusive scan -> k_rules_scan<1> (records in
 // (opening event, rule) order) -> run ids -> k_rules_keys -> stable LSD radix
 // sort of the records by (run, query, consuming event) -> k_rules_place.
+//
+// Streaming (sh_host_fast.cpp rules_step: rule sets beyond the general engine's
+// query table through sh_push_batch): the same pipeline over the carried opening
+// events followed by the staged send() calls, the scans in their CARRY form, then
+// k_carry_ids / k_rules_carry (the next carried state) and k_rules_klast.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -91,16 +96,32 @@ __device__ __forceinline__ int64_t rule_ix_key(int type, int64_t raw) {
     return (int64_t)(int32_t)raw;
 }
 
+// a row's surviving rule ids kept ascending (an event's candidate rules come as its
+// index group, then the rules without the indexed conjunct: two ascending runs)
+__device__ __forceinline__ void shr_put_sorted(uint32_t* __restrict__ a, uint32_t n, uint32_t r) {
+    uint32_t i = n;
+    while (i > 0 && a[i - 1] > r) {
+        a[i] = a[i - 1];
+        i--;
+    }
+    a[i] = r;
+}
+
 // WRITE = 0: matches opened at every key-segment position p -> cnt[p]
 // WRITE = 1: the same scan, writing (p, q, rule) records from off[p] on
-template <int WRITE>
+// CARRY = 1: a streaming step (shr_carry): rows below K.nc are carried opening
+// events -- no f1, only their live rules, never a consumer -- and each pass also
+// counts / writes the survivors. A partial whose walk reaches the end of its key's
+// events without a match and without expiring survives: the key's last event has
+// its greatest timestamp, so ts_last - ts_p <= W_r.
+template <int WRITE, int CARRY>
 __global__ void __launch_bounds__(RTPB) k_rules_scan(const shr_table* __restrict__ RT, const int64_t* __restrict__ sts,
                                                      const uint32_t* __restrict__ skeys, int64_t n, uint32_t sentinel,
                                                      const shd_cols* __restrict__ C, uint32_t* __restrict__ cnt,
                                                      const uint32_t* __restrict__ off, uint32_t* __restrict__ rec_p,
                                                      uint32_t* __restrict__ rec_q, uint32_t* __restrict__ rec_r,
                                                      int32_t* __restrict__ flag, const uint32_t* __restrict__ s32,
-                                                     int64_t tb) {
+                                                     int64_t tb, shr_carry K) {
     const int ix_attr = RT->ix_attr;
     const int n_ix = RT->n_ix;
     const uint32_t n_free = (uint32_t)RT->n_free;
@@ -116,13 +137,20 @@ __global__ void __launch_bounds__(RTPB) k_rules_scan(const shr_table* __restrict
     }
     __syncthreads();
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) {
-        if (WRITE && cnt[p] == 0) continue;
+        const uint32_t ap = CARRY ? (K.perm ? K.perm[p] : (uint32_t)p) : 0u;  // arrival index
+        if (WRITE && cnt[p] == 0 && (!CARRY || K.scnt[ap] == 0)) continue;
         const uint32_t key = skeys ? skeys[p] : 0u;
         if (key == sentinel) continue;
         const int64_t t0 = SHR_TS(p);
         if (!WRITE && p > 0 && (!skeys || skeys[p - 1] == key) && t0 < SHR_TS(p - 1)) atomicExch(flag, 1);
+        const bool carried = CARRY && ap < K.nc;
+        // (a key's first staged event against its last event of the earlier steps)
+        if (CARRY && !WRITE && !carried && t0 < K.klast[key]) atomicExch(flag, 1);
         uint32_t lo = 0, hi = 0;
-        if (ix_attr >= 0) {
+        if (carried) {
+            lo = K.c_off[ap];
+            hi = K.c_off[ap + 1];
+        } else if (ix_attr >= 0) {
             const int ty = RT->attr_type[ix_attr];
             const int64_t x = rule_ix_key(ty, load_attr(C, 0, ix_attr, ty, (uint32_t)p));
             int a = 0, b = n_ix;
@@ -152,18 +180,24 @@ __global__ void __launch_bounds__(RTPB) k_rules_scan(const shr_table* __restrict
                 }
             }
         }
-        const uint32_t nsel = hi - lo, total = nsel + n_free;
-        uint32_t c = 0;
+        const uint32_t nsel = hi - lo, total = carried ? nsel : nsel + n_free;
+        uint32_t c = 0, sc = 0;
         const uint32_t o = WRITE ? off[p] : 0u;
+        const uint32_t so = (CARRY && WRITE) ? K.soff[ap] : 0u;
         for (uint32_t k = 0; k < total; k++) {
-            const uint32_t r = k < nsel ? RT->ix_rule[lo + k] : RT->free_rule[k - nsel];
+            const uint32_t r = carried ? K.c_rule[lo + k] : (k < nsel ? RT->ix_rule[lo + k] : RT->free_rule[k - nsel]);
             const shr_rule* R = RT->rules + r;
-            if (!rule_terms(R->t[0], R->nt[0], (uint32_t)p, SHD_NULL_ROW, C)) continue;
+            if (!carried && !rule_terms(R->t[0], R->nt[0], (uint32_t)p, SHD_NULL_ROW, C)) continue;
             const int64_t W = R->within;
+            bool live = true;
             for (int64_t q = p + 1; q < n; q++) {
                 if (skeys && skeys[q] != key) break;
                 const int64_t d = SHR_TS(q) - t0;
-                if (W >= 0 && (d < 0 ? -d : d) > W) break;  // expired before event q is matched
+                if (W >= 0 && (d < 0 ? -d : d) > W) {  // expired before event q is matched
+                    live = false;
+                    break;
+                }
+                if (CARRY && (K.perm ? K.perm[q] : (uint32_t)q) < K.nc) continue;  // a carried row never consumes
                 if (rule_terms(R->t[1], R->nt[1], (uint32_t)p, (uint32_t)q, C)) {
                     if (WRITE) {
                         rec_p[o + c] = (uint32_t)p;
@@ -171,11 +205,17 @@ __global__ void __launch_bounds__(RTPB) k_rules_scan(const shr_table* __restrict
                         rec_r[o + c] = r;
                     }
                     c++;
+                    live = false;
                     break;
                 }
             }
+            if (CARRY && live) {
+                if (WRITE) shr_put_sorted(K.s_rule + so, sc, r);
+                sc++;
+            }
         }
         if (!WRITE) cnt[p] = c;
+        if (CARRY && !WRITE) K.scnt[ap] = sc;
     }
 }
 
@@ -287,12 +327,12 @@ __device__ __forceinline__ bool rule_terms_img(const shp_term* T, int nt, uint32
 }
 
 // OCC2: the image fits two workgroups per CU, registers capped for 8 waves per SIMD
-template <int WRITE, int OCC2>
+template <int WRITE, int OCC2, int CARRY>
 __global__ void __launch_bounds__(RTPB_IMG) __attribute__((amdgpu_waves_per_eu(OCC2 ? 8 : 1))) k_rules_scan_img(
     const shr_table* __restrict__ RT, const int64_t* __restrict__ sts, const uint32_t* __restrict__ skeys, int64_t n,
     uint32_t sentinel, const shd_cols* __restrict__ C, uint32_t* __restrict__ cnt, const uint32_t* __restrict__ off,
     uint32_t* __restrict__ rec_p, uint32_t* __restrict__ rec_q, uint32_t* __restrict__ rec_r, int32_t* __restrict__ flag,
-    const uint8_t* __restrict__ img, shr_img I, const uint32_t* __restrict__ s32, int64_t tb) {
+    const uint8_t* __restrict__ img, shr_img I, const uint32_t* __restrict__ s32, int64_t tb, shr_carry K) {
     extern __shared__ uint4 s_img[];
     __shared__ const void* s_col[32];
     for (int i = threadIdx.x; i < I.lds / 16; i += blockDim.x) s_img[i] = ((const uint4*)img)[i];
@@ -312,13 +352,20 @@ __global__ void __launch_bounds__(RTPB_IMG) __attribute__((amdgpu_waves_per_eu(O
     const uint32_t n_free = (uint32_t)RT->n_free;
     const int ix_ty = ix_attr >= 0 ? RT->attr_type[ix_attr] : 0;
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) {
-        if (WRITE && cnt[p] == 0) continue;
+        const uint32_t ap = CARRY ? (K.perm ? K.perm[p] : (uint32_t)p) : 0u;  // arrival index
+        if (WRITE && cnt[p] == 0 && (!CARRY || K.scnt[ap] == 0)) continue;
         const uint32_t key = skeys ? skeys[p] : 0u;
         if (key == sentinel) continue;
         const int64_t t0 = SHR_TS(p);
         if (!WRITE && p > 0 && (!skeys || skeys[p - 1] == key) && t0 < SHR_TS(p - 1)) atomicExch(flag, 1);
+        const bool carried = CARRY && ap < K.nc;
+        // (a key's first staged event against its last event of the earlier steps)
+        if (CARRY && !WRITE && !carried && t0 < K.klast[key]) atomicExch(flag, 1);
         uint32_t lo = 0, hi = 0;
-        if (ix_attr >= 0) {
+        if (carried) {
+            lo = K.c_off[ap];
+            hi = K.c_off[ap + 1];
+        } else if (ix_attr >= 0) {
             const int64_t x = rule_ix_key(ix_ty, rule_attr(s_col, ix_attr, ix_ty, (uint32_t)p));
             if (I.dense_n) {
                 const int64_t dv = x - I.dense_min;
@@ -342,19 +389,25 @@ __global__ void __launch_bounds__(RTPB_IMG) __attribute__((amdgpu_waves_per_eu(O
                 }
             }
         }
-        const uint32_t nsel = hi - lo, total = nsel + n_free;
-        uint32_t c = 0;
+        const uint32_t nsel = hi - lo, total = carried ? nsel : nsel + n_free;
+        uint32_t c = 0, sc = 0;
         const uint32_t o = WRITE ? off[p] : 0u;
+        const uint32_t so = (CARRY && WRITE) ? K.soff[ap] : 0u;
         for (uint32_t k = 0; k < total; k++) {
-            const uint32_t r = k < nsel ? ixr[lo + k] : fr[k - nsel];
+            const uint32_t r = carried ? K.c_rule[lo + k] : (k < nsel ? ixr[lo + k] : fr[k - nsel]);
             const shr_meta M = meta[r];
-            if (!rule_terms_img(terms0 + M.toff0, M.nt0, (uint32_t)p, SHD_NULL_ROW, s_col)) continue;
+            if (!carried && !rule_terms_img(terms0 + M.toff0, M.nt0, (uint32_t)p, SHD_NULL_ROW, s_col)) continue;
             const shp_term* T1 = terms1 + M.toff1;
             const int64_t W = M.within;
+            bool live = true;
             for (int64_t q = p + 1; q < n; q++) {
                 if (skeys && skeys[q] != key) break;
                 const int64_t d = SHR_TS(q) - t0;
-                if (W >= 0 && (d < 0 ? -d : d) > W) break;  // expired before event q is matched
+                if (W >= 0 && (d < 0 ? -d : d) > W) {  // expired before event q is matched
+                    live = false;
+                    break;
+                }
+                if (CARRY && (K.perm ? K.perm[q] : (uint32_t)q) < K.nc) continue;  // a carried row never consumes
                 if (rule_terms_img(T1, M.nt1, (uint32_t)p, (uint32_t)q, s_col)) {
                     if (WRITE) {
                         rec_p[o + c] = (uint32_t)p;
@@ -362,24 +415,33 @@ __global__ void __launch_bounds__(RTPB_IMG) __attribute__((amdgpu_waves_per_eu(O
                         rec_r[o + c] = r;
                     }
                     c++;
+                    live = false;
                     break;
                 }
             }
+            if (CARRY && live) {
+                if (WRITE) shr_put_sorted(K.s_rule + so, sc, r);
+                sc++;
+            }
         }
         if (!WRITE) cnt[p] = c;
+        if (CARRY && !WRITE) K.scnt[ap] = sc;
     }
 }
 
-template <int WRITE>
+template <int WRITE, int CARRY>
 static int rules_scan_img(const shr_table* dT, const int64_t* sts, const uint32_t* skeys, int64_t n, uint32_t sentinel,
                           const shd_cols* dC, uint32_t* cnt, const uint32_t* off, uint32_t* rec_p, uint32_t* rec_q,
                           uint32_t* rec_r, int32_t* flag, const uint8_t* img, const shr_img& I, hipStream_t st,
-                          const uint32_t* s32, int64_t tb) {
+                          const uint32_t* s32, int64_t tb, const shr_carry& K) {
+    // a streaming step (CARRY) always takes the uncapped variant: under the 64-register
+    // cap of OCC2 the carried-prefix branches would spill 14 / 24 VGPRs to scratch
+    constexpr int OCC2_OK = CARRY ? 0 : 1;
     static int attr_set = 0;  // the dynamic LDS limit, raised once per instantiation
     if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rules_scan_img<WRITE, 0>),
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rules_scan_img<WRITE, 0, CARRY>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, SHR_IMG_MAX) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rules_scan_img<WRITE, 1>),
+            hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rules_scan_img<WRITE, OCC2_OK, CARRY>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, SHR_IMG_MAX) != hipSuccess)
             return -3;
         attr_set = 1;
@@ -390,12 +452,12 @@ static int rules_scan_img(const shr_table* dT, const int64_t* sts, const uint32_
     if (g > gmax) g = gmax;
     if (g < 1) g = 1;
     static const bool occ_on = !(getenv("SH_RULES_OCC2") && getenv("SH_RULES_OCC2")[0] == '0');
-    if (per_cu >= 2 && occ_on)
-        hipLaunchKernelGGL((k_rules_scan_img<WRITE, 1>), dim3((unsigned)g), dim3(RTPB_IMG), (size_t)I.lds, st, dT, sts,
-                           skeys, n, sentinel, dC, cnt, off, rec_p, rec_q, rec_r, flag, img, I, s32, tb);
+    if (per_cu >= 2 && occ_on && OCC2_OK)
+        hipLaunchKernelGGL((k_rules_scan_img<WRITE, OCC2_OK, CARRY>), dim3((unsigned)g), dim3(RTPB_IMG), (size_t)I.lds, st, dT,
+                           sts, skeys, n, sentinel, dC, cnt, off, rec_p, rec_q, rec_r, flag, img, I, s32, tb, K);
     else
-        hipLaunchKernelGGL((k_rules_scan_img<WRITE, 0>), dim3((unsigned)g), dim3(RTPB_IMG), (size_t)I.lds, st, dT, sts,
-                           skeys, n, sentinel, dC, cnt, off, rec_p, rec_q, rec_r, flag, img, I, s32, tb);
+        hipLaunchKernelGGL((k_rules_scan_img<WRITE, 0, CARRY>), dim3((unsigned)g), dim3(RTPB_IMG), (size_t)I.lds, st, dT,
+                           sts, skeys, n, sentinel, dC, cnt, off, rec_p, rec_q, rec_r, flag, img, I, s32, tb, K);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
@@ -545,12 +607,14 @@ __global__ void k_rules_place(const shr_table* __restrict__ RT, const uint32_t* 
                               const int64_t* __restrict__ sts, const shd_cols* __restrict__ C, uint64_t seq_base,
                               int n_out, uint64_t* __restrict__ out_seq, int32_t* __restrict__ out_query,
                               int64_t* __restrict__ out_ts, int64_t* __restrict__ out_vals,
-                              const uint32_t* __restrict__ s32, int64_t tb) {
+                              const uint32_t* __restrict__ s32, int64_t tb, const uint64_t* __restrict__ seqs) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
         const uint32_t id = order ? order[i] : (uint32_t)i;
         const uint32_t p = rec_p[id], q = rec_q[id];
         const shr_rule* R = RT->rules + rec_r[id];
-        if (out_seq) out_seq[i] = seq_base + (perm ? perm[q] : q);
+        // seqs: every event's own sequence number by arrival index (a streaming step:
+        // dropped null-key events took numbers too)
+        if (out_seq) out_seq[i] = seqs ? seqs[perm ? perm[q] : q] : seq_base + (perm ? perm[q] : q);
         if (out_query) out_query[i] = R->query;
         if (out_ts) out_ts[i] = SHR_TS(q);
         if (out_vals)
@@ -576,25 +640,48 @@ static unsigned sgrid(int64_t n) {
 
 extern "C" int shr_count(const shr_table* dT, const int64_t* sts, const uint32_t* skeys, int64_t n, uint32_t sentinel,
                          const shd_cols* dC, uint32_t* cnt, int32_t* flag, void* stream, const uint8_t* img,
-                         const shr_img* I, const uint32_t* s32, int64_t tb) {
-    if (img && I && I->bytes > 0)
-        return rules_scan_img<0>(dT, sts, skeys, n, sentinel, dC, cnt, nullptr, nullptr, nullptr, nullptr, flag, img, *I,
-                                 (hipStream_t)stream, s32, tb);
-    hipLaunchKernelGGL(k_rules_scan<0>, dim3(sgrid(n)), dim3(RTPB), 0, (hipStream_t)stream, dT, sts, skeys, n,
+                         const shr_img* I, const uint32_t* s32, int64_t tb, const shr_carry* K) {
+    const bool use_img = img && I && I->bytes > 0;
+    shr_carry none;
+    memset(&none, 0, sizeof(none));
+    if (K) {
+        if (use_img)
+            return rules_scan_img<0, 1>(dT, sts, skeys, n, sentinel, dC, cnt, nullptr, nullptr, nullptr, nullptr, flag,
+                                        img, *I, (hipStream_t)stream, s32, tb, *K);
+        hipLaunchKernelGGL((k_rules_scan<0, 1>), dim3(sgrid(n)), dim3(RTPB), 0, (hipStream_t)stream, dT, sts, skeys, n,
+                           sentinel, dC, cnt, (const uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
+                           (uint32_t*)nullptr, flag, s32, tb, *K);
+        return rules_ok();
+    }
+    if (use_img)
+        return rules_scan_img<0, 0>(dT, sts, skeys, n, sentinel, dC, cnt, nullptr, nullptr, nullptr, nullptr, flag, img,
+                                    *I, (hipStream_t)stream, s32, tb, none);
+    hipLaunchKernelGGL((k_rules_scan<0, 0>), dim3(sgrid(n)), dim3(RTPB), 0, (hipStream_t)stream, dT, sts, skeys, n,
                        sentinel, dC, cnt, (const uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                       (uint32_t*)nullptr, flag, s32, tb);
+                       (uint32_t*)nullptr, flag, s32, tb, none);
     return rules_ok();
 }
 
 extern "C" int shr_write(const shr_table* dT, const int64_t* sts, const uint32_t* skeys, int64_t n, uint32_t sentinel,
                          const shd_cols* dC, const uint32_t* cnt, const uint32_t* off, uint32_t* rec_p,
                          uint32_t* rec_q, uint32_t* rec_r, void* stream, const uint8_t* img, const shr_img* I,
-                         const uint32_t* s32, int64_t tb) {
-    if (img && I && I->bytes > 0)
-        return rules_scan_img<1>(dT, sts, skeys, n, sentinel, dC, (uint32_t*)cnt, off, rec_p, rec_q, rec_r, nullptr,
-                                 img, *I, (hipStream_t)stream, s32, tb);
-    hipLaunchKernelGGL(k_rules_scan<1>, dim3(sgrid(n)), dim3(RTPB), 0, (hipStream_t)stream, dT, sts, skeys, n,
-                       sentinel, dC, (uint32_t*)cnt, off, rec_p, rec_q, rec_r, (int32_t*)nullptr, s32, tb);
+                         const uint32_t* s32, int64_t tb, const shr_carry* K) {
+    const bool use_img = img && I && I->bytes > 0;
+    shr_carry none;
+    memset(&none, 0, sizeof(none));
+    if (K) {
+        if (use_img)
+            return rules_scan_img<1, 1>(dT, sts, skeys, n, sentinel, dC, (uint32_t*)cnt, off, rec_p, rec_q, rec_r,
+                                        nullptr, img, *I, (hipStream_t)stream, s32, tb, *K);
+        hipLaunchKernelGGL((k_rules_scan<1, 1>), dim3(sgrid(n)), dim3(RTPB), 0, (hipStream_t)stream, dT, sts, skeys, n,
+                           sentinel, dC, (uint32_t*)cnt, off, rec_p, rec_q, rec_r, (int32_t*)nullptr, s32, tb, *K);
+        return rules_ok();
+    }
+    if (use_img)
+        return rules_scan_img<1, 0>(dT, sts, skeys, n, sentinel, dC, (uint32_t*)cnt, off, rec_p, rec_q, rec_r, nullptr,
+                                    img, *I, (hipStream_t)stream, s32, tb, none);
+    hipLaunchKernelGGL((k_rules_scan<1, 0>), dim3(sgrid(n)), dim3(RTPB), 0, (hipStream_t)stream, dT, sts, skeys, n,
+                       sentinel, dC, (uint32_t*)cnt, off, rec_p, rec_q, rec_r, (int32_t*)nullptr, s32, tb, none);
     return rules_ok();
 }
 
@@ -628,9 +715,10 @@ extern "C" int shr_gather(const uint32_t* key, const uint32_t* order, int64_t m,
 extern "C" int shr_place(const shr_table* dT, const uint32_t* order, int64_t m, const uint32_t* rec_p,
                          const uint32_t* rec_q, const uint32_t* rec_r, const uint32_t* perm, const int64_t* sts,
                          const shd_cols* dC, uint64_t seq_base, int n_out, uint64_t* out_seq, int32_t* out_query,
-                         int64_t* out_ts, int64_t* out_vals, void* stream, const uint32_t* s32, int64_t tb) {
+                         int64_t* out_ts, int64_t* out_vals, void* stream, const uint32_t* s32, int64_t tb,
+                         const uint64_t* seqs) {
     hipLaunchKernelGGL(k_rules_place, dim3(rgrid(m)), dim3(RTPB), 0, (hipStream_t)stream, dT, order, m, rec_p, rec_q,
-                       rec_r, perm, sts, dC, seq_base, n_out, out_seq, out_query, out_ts, out_vals, s32, tb);
+                       rec_r, perm, sts, dC, seq_base, n_out, out_seq, out_query, out_ts, out_vals, s32, tb, seqs);
     return rules_ok();
 }
 
@@ -682,6 +770,122 @@ extern "C" int shr_ts_to32(const int64_t* ts, int64_t n, int64_t base, uint32_t*
     return rules_ok();
 }
 
+// ---------------------------------------------------------------- carried state of a streaming step
+// After the scans of a step (CARRY = 1) the survivors are known per arrival index:
+// scnt[i] partials, their rule ids at s_rule[soff[i] ..) -- already in (row, rule)
+// order, because soff is a scan in arrival order. What is left is the rows: the
+// opening events that still hold a partial are kept once each, in arrival order
+// (the opening event is the last key of the output order, so the compaction is
+// order preserving), in the other half of the double-buffered carry store.
+#define CTPB 1024
+
+// new row ids, workgroup-local: the exclusive scan of the "row survives" flags of
+// CTPB rows (wave DPP scans + one LDS word per wave), and the workgroup's total
+__global__ void __launch_bounds__(CTPB) k_carry_ids(const uint32_t* __restrict__ scnt, int64_t n,
+                                                    uint32_t* __restrict__ lid, uint32_t* __restrict__ blk) {
+    __shared__ uint32_t s_ws[CTPB / 64];
+    const int64_t i = (int64_t)blockIdx.x * CTPB + threadIdx.x;
+    const uint32_t f = (i < n && scnt[i] != 0u) ? 1u : 0u;
+    uint32_t tot;
+    const uint32_t e = shw_block_excl<CTPB>(f, s_ws, &tot);
+    if (i < n) lid[i] = e;
+    if (threadIdx.x == 0) blk[blockIdx.x] = tot;
+}
+
+// the surviving rows gathered into the next carry store: row i of the step's
+// concatenated columns -> row blk_off[block] + lid[i], with its timestamp, key,
+// sequence number, attribute columns and the start of its rule list
+struct shr_carry_cols {
+    const void* src[8];
+    void* dst[8];
+    int32_t width[8];
+    int32_t n;
+    int32_t pad;
+};
+
+__global__ void __launch_bounds__(CTPB) k_rules_carry(const uint32_t* __restrict__ scnt,
+                                                      const uint32_t* __restrict__ soff, int64_t n,
+                                                      const uint32_t* __restrict__ lid,
+                                                      const uint32_t* __restrict__ blk_off,
+                                                      const int64_t* __restrict__ ts, const int32_t* __restrict__ key,
+                                                      const uint64_t* __restrict__ seq, int64_t* __restrict__ n_ts,
+                                                      int32_t* __restrict__ n_key, uint64_t* __restrict__ n_seq,
+                                                      uint32_t* __restrict__ n_off, shr_carry_cols CC) {
+    const int64_t i = (int64_t)blockIdx.x * CTPB + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t j = blk_off[blockIdx.x] + lid[i];
+    // the list's end, behind the last kept row (blk_off has one entry past the last workgroup)
+    if (i == n - 1) n_off[blk_off[gridDim.x]] = soff[n];
+    if (scnt[i] == 0u) return;
+    n_ts[j] = ts[i];
+    n_key[j] = key[i];
+    n_seq[j] = seq[i];
+    n_off[j] = soff[i];
+    for (int c = 0; c < CC.n; c++) {
+        switch (CC.width[c]) {
+            case 8: ((uint64_t*)CC.dst[c])[j] = ((const uint64_t*)CC.src[c])[i]; break;
+            case 4: ((uint32_t*)CC.dst[c])[j] = ((const uint32_t*)CC.src[c])[i]; break;
+            default: ((uint8_t*)CC.dst[c])[j] = ((const uint8_t*)CC.src[c])[i]; break;
+        }
+    }
+}
+
+// per key the timestamp of its last event: the last staged row of each key's run
+// in key-segment order (skeys NULL: one key, the last row)
+__global__ void k_rules_klast(const int64_t* __restrict__ sts, const uint32_t* __restrict__ skeys,
+                              const uint32_t* __restrict__ perm, int64_t n, uint32_t nc, int64_t* __restrict__ klast) {
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) {
+        if ((perm ? perm[p] : (uint32_t)p) < nc) continue;
+        const uint32_t key = skeys ? skeys[p] : 0u;
+        if (p + 1 < n && (!skeys || skeys[p + 1] == key)) continue;
+        klast[key] = sts[p];
+    }
+}
+
+__global__ void k_fill_i64(int64_t* __restrict__ a, int64_t n, int64_t v) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        a[i] = v;
+}
+
+extern "C" int64_t shr_carry_blocks(int64_t n) { return (n + CTPB - 1) / CTPB; }
+
+extern "C" int shr_carry_ids(const uint32_t* scnt, int64_t n, uint32_t* lid, uint32_t* blk, void* stream) {
+    hipLaunchKernelGGL(k_carry_ids, dim3((unsigned)shr_carry_blocks(n)), dim3(CTPB), 0, (hipStream_t)stream, scnt, n,
+                       lid, blk);
+    return rules_ok();
+}
+
+extern "C" int shr_carry_rows(const uint32_t* scnt, const uint32_t* soff, int64_t n, const uint32_t* lid,
+                              const uint32_t* blk_off, const int64_t* ts, const int32_t* key, const uint64_t* seq,
+                              int64_t* n_ts, int32_t* n_key, uint64_t* n_seq, uint32_t* n_off, int n_cols,
+                              const void* const* src, void* const* dst, const int32_t* width, void* stream) {
+    if (n_cols > 8) return 1;
+    shr_carry_cols CC;
+    memset(&CC, 0, sizeof(CC));
+    CC.n = n_cols;
+    for (int c = 0; c < n_cols; c++) {
+        CC.src[c] = src[c];
+        CC.dst[c] = dst[c];
+        CC.width[c] = width[c];
+    }
+    hipLaunchKernelGGL(k_rules_carry, dim3((unsigned)shr_carry_blocks(n)), dim3(CTPB), 0, (hipStream_t)stream, scnt,
+                       soff, n, lid, blk_off, ts, key, seq, n_ts, n_key, n_seq, n_off, CC);
+    return rules_ok();
+}
+
+extern "C" int shr_klast_update(const int64_t* sts, const uint32_t* skeys, const uint32_t* perm, int64_t n, uint32_t nc,
+                                int64_t* klast, void* stream) {
+    hipLaunchKernelGGL(k_rules_klast, dim3(rgrid(n)), dim3(RTPB), 0, (hipStream_t)stream, sts, skeys, perm, n, nc,
+                       klast);
+    return rules_ok();
+}
+
+extern "C" int shr_fill_i64(int64_t* a, int64_t n, int64_t v, void* stream) {
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(k_fill_i64, dim3(rgrid(n)), dim3(RTPB), 0, (hipStream_t)stream, a, n, v);
+    return rules_ok();
+}
+
 // ---------------------------------------------------------------- sparse partials
 // The same matches without a key segment, for partitioned rule sets whose start
 // filters open few partials (C5: `amount > A and merchant == M` holds for ~2% of
@@ -697,9 +901,10 @@ extern "C" int shr_ts_to32(const int64_t* ts, int64_t n, int64_t base, uint32_t*
 //   k_sparse_place: the partials into their keys' lists, with their expiry time;
 //   k_sparse_take: per event q, its key's partials opened before it that are not
 //     expired at ts_q and whose f2 holds -> atomicMin of q into the partial;
-//   k_sparse_rec: the taken partials -> (p, q, r) records (any order: the host
-//     sorts them by p first, which restores the (opening event, rule) order the
-//     record sort's stability relies on).
+//   k_sparse_rec: the taken partials -> (p, q, r) records, in any order: after
+//     the stable passes by (run, rule, consuming event) k_rules_ties puts each run
+//     of equal keys in opening-event order, which gives the same total order as
+//     records written in (opening event, rule) order.
 // A run whose timestamps decrease, whose keys leave [0, nkeys), or whose partials
 // overflow the buffers (the host reads the count) sets a flag: the host runs the
 // key-segment path instead.
