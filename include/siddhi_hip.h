@@ -88,7 +88,7 @@ int sh_start(sh_handle* h);
    sh_run_device -- and the handle keeps the state from before the failed batch.
 
    Rule sets beyond the general engine's query table (more than 16 queries, each
-   `every e1=S[f1] -> e2=S[f2(e1, e2)] within W`, no aggregators) stream through
+   `every e1=S[f1] -> e2=S[f2(e1, e2)] within W`) stream through
    the rule engine: a call on stream 0 is one send(Event[]) call, of any size, and
    is staged with each event's own sequence number (an event whose key is -1 is
    dropped: it takes a number, and it ends the run of same-key events around
@@ -104,8 +104,11 @@ int sh_start(sh_handle* h);
    fails with SH_E_UNSUPPORTED when timestamps decrease inside a key (also
    against the key's last event of an earlier step) or a batch's null mask has
    a set bit; the staged calls are then dropped, sequence numbers included, and
-   the carried state is what it was before them. Aggregating rule sets of that
-   size are refused here (SH_E_UNSUPPORTED): sh_run_device only. sh_start and
+   the carried state is what it was before them. A set whose selects aggregate
+   (sum / avg / count, one aggregate layout for the whole set) also carries one
+   running state per (query, partition key) that ever produced a row, and adds
+   each step's rows to it one at a time in output order, as the reference does;
+   a refused step leaves these states alone too. sh_start and
    sh_advance_time do nothing for such a handle and sh_set_coordinator refuses it. */
 int sh_push_batch(sh_handle* h, const sh_batch* batch);
 

@@ -178,6 +178,10 @@ def bind_product(lib):
     lib.shx_rules_status.restype = C.c_int
     lib.shx_rules_carry.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.shx_rules_carry.restype = C.c_int
+    lib.shx_rules_agg_carry.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+    lib.shx_rules_agg_carry.restype = C.c_int
+    lib.shx_rules_agg_capacity.argtypes = [C.c_void_p]
+    lib.shx_rules_agg_capacity.restype = C.c_int64
     lib.shx_host_profile.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.shx_host_profile.restype = C.c_int
     lib.shx_seq3_shape.argtypes = [C.c_void_p]

@@ -26,8 +26,9 @@ int64_t sha_scratch_bytes(int64_t m, int n_cols);
 // d_query the emitting query or NULL): each listed column's argument values
 // become the running aggregate per (query, partition key of the trigger event
 // = d_keys[seq - seq_base], NULL: one key). 0: done; 1: the double additions
-// would round (or NaN / infinite addends): nothing usable was written, run the
-// query sequentially; < 0: error.
+// would round (or NaN / infinite addends): the rows are as they were, run the
+// query sequentially (sh_agg_seq.h shc_running, or a sequential engine); < 0:
+// error. On 0 the last launch (the rows' scatter) is still in flight on `stream`.
 int sha_running(const uint64_t* d_seq, int64_t* d_vals, int32_t n_out, int64_t m, const int32_t* d_query,
                 int32_t n_query, const int32_t* d_keys, int32_t n_keys, uint64_t seq_base, const sha_desc* D,
                 void* d_scratch, void* stream);

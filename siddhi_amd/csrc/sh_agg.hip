@@ -23,7 +23,9 @@
 // one of the reference's additions was exact and its results equal these bit
 // for bit. Otherwise (or with NaN / infinite addends, or a fixed-point range
 // over 96 bits) the pass reports "not exact" and the caller reruns the query on
-// an engine that adds sequentially.
+// an engine that adds sequentially -- for a rule set beyond the general engine's
+// query table, the carried sequential pass at the end of this file, which also
+// keeps such a set's aggregates between streaming steps.
 //
 // Pipeline: k_sha_prep (segment id = query * nkeys + key of the trigger event,
 // exponent range per column) -> stable radix sort of (segment, row) ->
@@ -39,6 +41,7 @@
 
 #include "../../include/sh_query.h"
 #include "sh_agg.h"
+#include "sh_agg_seq.h"
 #include "sh_device.h"
 
 #define SHA_TPB 256
@@ -514,11 +517,208 @@ extern "C" int sha_running(const uint64_t* d_seq, int64_t* d_vals, int32_t n_out
                            (const int64_t*)sc, (const sha_el*)tiles, (const uint32_t*)fh, range + 3 * SHA_MAX_COLS);
         if (sha_ok()) return -3;
     }
-    hipLaunchKernelGGL(k_sha_scatter, dim3(g), dim3(SHA_TPB), 0, st, d_vals, n_out, sidx, m, *D,
-                       (const int64_t*)scol);
-    if (sha_ok()) return -3;
+    // the rows are written only once every addition is known to be exact: a "not
+    // exact" answer leaves the aggregators' arguments in place for the sequential
+    // pass (shc_running)
     int32_t inexact = 0;
     hipMemcpyAsync(&inexact, range + 3 * SHA_MAX_COLS, 4, hipMemcpyDeviceToHost, st);
     if (hipStreamSynchronize(st) != hipSuccess) return -3;
-    return inexact ? 1 : 0;
+    if (inexact) return 1;
+    hipLaunchKernelGGL(k_sha_scatter, dim3(g), dim3(SHA_TPB), 0, st, d_vals, n_out, sidx, m, *D,
+                       (const int64_t*)scol);
+    if (sha_ok()) return -3;
+    return 0;
+}
+
+// ---------------------------------------------------------------- carried, sequential pass
+// The same rows with no exactness proof: the reference's additions one at a time
+// (sh_agg_seq.h), one lane per (query, key) segment, starting from the segment's
+// carried state. Behind streaming rule sets (rules_step: the state of every
+// (query, key) that ever produced a row lives in an open-addressing table in HBM)
+// and behind sh_run_device when the parallel pass above answers "not exact" (no
+// table: every segment starts from zero).
+//
+// Pipeline: k_shc_prep (key and query of every row) -> stable radix sort by key,
+// then by query (LSD: the rows of a segment keep their output order, which is the
+// addition order) -> k_shc_gather (aggregate columns and 64-bit segment keys into
+// sorted order) -> k_shc_walk (segment heads: look the carried state up, walk the
+// run, running values into the columns, final state and segment key aside) ->
+// k_sha_scatter. The table is not written here: shc_put (k_shc_put) inserts the
+// heads' final states, and the caller launches it last, when nothing can refuse
+// the step any more. A segment has one head, so no two lanes write one entry; a
+// slot is claimed with a 64-bit compare-and-swap on its key.
+__global__ void __launch_bounds__(SHA_TPB) k_shc_prep(const uint64_t* __restrict__ seq, int64_t m,
+                                                      const int32_t* __restrict__ query,
+                                                      const int32_t* __restrict__ rowkey,
+                                                      const int32_t* __restrict__ keys, uint64_t seq_base,
+                                                      uint32_t* __restrict__ klo, uint32_t* __restrict__ khi,
+                                                      uint32_t* __restrict__ idx) {
+    const int64_t r = (int64_t)blockIdx.x * SHA_TPB + threadIdx.x;
+    if (r >= m) return;
+    klo[r] = rowkey ? (uint32_t)rowkey[r] : keys ? (uint32_t)keys[seq[r] - seq_base] : 0u;
+    khi[r] = query ? (uint32_t)query[r] : 0u;
+    idx[r] = (uint32_t)r;
+}
+
+// (order and gv may be one array: a lane reads its entry before it writes it)
+__global__ void __launch_bounds__(SHA_TPB) k_shc_pick(const uint32_t* __restrict__ key, const uint32_t* order,
+                                                      int64_t m, uint32_t* __restrict__ gk, uint32_t* gv) {
+    const int64_t p = (int64_t)blockIdx.x * SHA_TPB + threadIdx.x;
+    if (p >= m) return;
+    const uint32_t r = order[p];
+    gk[p] = key[r];
+    gv[p] = r;
+}
+
+__global__ void __launch_bounds__(SHA_TPB) k_shc_gather(const int64_t* __restrict__ vals, int n_out,
+                                                        const uint32_t* __restrict__ idx, int64_t m, sha_desc D,
+                                                        const uint32_t* __restrict__ klo,
+                                                        const uint32_t* __restrict__ khi, int64_t* __restrict__ sc,
+                                                        uint64_t* __restrict__ sseg) {
+    const int64_t p = (int64_t)blockIdx.x * SHA_TPB + threadIdx.x;
+    if (p >= m) return;
+    const uint32_t r = idx[p];
+    const int64_t* row = vals + (int64_t)r * n_out;
+    for (int k = 0; k < D.n_cols; k++) sc[(int64_t)k * m + p] = row[D.c[k].col];
+    sseg[p] = shq_key((int32_t)khi[r], (int32_t)klo[r]);
+}
+
+// pk[p]: the segment key at a head, SHQ_EMPTY elsewhere; fin: the heads' final states
+__global__ void __launch_bounds__(SHA_TPB) k_shc_walk(int64_t* __restrict__ sc, const uint64_t* __restrict__ sseg,
+                                                      int64_t m, sha_desc D, shq_table T, uint64_t* __restrict__ pk,
+                                                      int64_t* __restrict__ fin) {
+    const int64_t p = (int64_t)blockIdx.x * SHA_TPB + threadIdx.x;
+    if (p >= m) return;
+    const uint64_t sg = sseg[p];
+    if (p > 0 && sseg[p - 1] == sg) {
+        pk[p] = SHQ_EMPTY;
+        return;
+    }
+    pk[p] = sg;
+    int64_t e = p + 1;
+    while (e < m && sseg[e] == sg) e++;
+    const int64_t slot = shq_find(T, sg);
+    // column by column: the running state stays in registers
+    for (int k = 0; k < D.n_cols; k++)
+        shq_walk(sc + (int64_t)k * m, p, e, D.c[k], T, slot, k, fin + (p * D.n_cols + k) * 2);
+}
+
+// entries (pk[i] != SHQ_EMPTY) with their states into the table; *entries counts
+// the slots claimed, *err |= 1 when a probe found no slot (the caller keeps the
+// table at most half full, so that is a bug, not a state)
+__global__ void __launch_bounds__(SHA_TPB) k_shc_put(shq_table T, const uint64_t* __restrict__ pk,
+                                                     const int64_t* __restrict__ fin, int64_t n,
+                                                     unsigned long long* __restrict__ entries,
+                                                     int32_t* __restrict__ err) {
+    const int64_t i = (int64_t)blockIdx.x * SHA_TPB + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t key = pk[i];
+    if (key == SHQ_EMPTY) return;
+    const uint64_t mask = (uint64_t)T.cap - 1ull;
+    uint64_t s = shq_hash(key) & mask;
+    int64_t slot = -1;
+    for (int64_t t = 0; t < T.cap; t++) {
+        const unsigned long long was =
+            atomicCAS((unsigned long long*)&T.keys[s], (unsigned long long)SHQ_EMPTY, (unsigned long long)key);
+        if (was == (unsigned long long)SHQ_EMPTY) {
+            atomicAdd(entries, 1ull);
+            slot = (int64_t)s;
+            break;
+        }
+        if (was == (unsigned long long)key) {
+            slot = (int64_t)s;
+            break;
+        }
+        s = (s + 1ull) & mask;
+    }
+    if (slot < 0) {
+        atomicOr(err, 1);
+        return;
+    }
+    for (int k = 0; k < T.n_cols * 2; k++) T.state[slot * T.n_cols * 2 + k] = fin[i * T.n_cols * 2 + k];
+}
+
+extern "C" int64_t shc_scratch_bytes(int64_t m, int n_cols) {
+    const int64_t rt = (m + 4095) / 4096;
+    const int64_t nc = n_cols < 1 ? 1 : n_cols;
+    // key, query, idx, picked keys, 2 x 2 sort buffers; sort histogram and scan
+    // temporaries; the sorted column copies; segment keys, head keys, final states
+    return m * 4 * 8 + 256 * rt * 4 + (int64_t)shd_scan_tmp_words(256 * rt) * 4 + nc * m * 8 + m * 8 * 2 +
+           nc * m * 16 + 256 * 16;
+}
+
+extern "C" int shc_running(const uint64_t* d_seq, int64_t* d_vals, int32_t n_out, int64_t m, const int32_t* d_query,
+                           int32_t n_query, const int32_t* d_rowkey, const int32_t* d_keys, int32_t n_keys,
+                           uint64_t seq_base, const sha_desc* D, const shq_table* T, void* d_scratch, void* stream,
+                           const uint64_t** put_keys, const int64_t** put_state) {
+    if (put_keys) *put_keys = nullptr;
+    if (put_state) *put_state = nullptr;
+    if (m <= 0 || D->n_cols == 0) return 0;
+    if (m >= ((int64_t)1 << 31) || n_out < 1 || !d_vals || !d_scratch || (!d_rowkey && d_keys && !d_seq)) return -1;
+    if (T && T->cap > 0 && ((T->cap & (T->cap - 1)) || T->n_cols != D->n_cols || !T->keys || !T->state)) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t rt = (m + 4095) / 4096;
+    uint8_t* p = (uint8_t*)d_scratch;
+    auto take = [&](int64_t bytes) {
+        uint8_t* r = p;
+        p += (bytes + 255) & ~(int64_t)255;
+        return (void*)r;
+    };
+    uint32_t* klo = (uint32_t*)take(m * 4);
+    uint32_t* khi = (uint32_t*)take(m * 4);
+    uint32_t* idx = (uint32_t*)take(m * 4);
+    uint32_t* gk = (uint32_t*)take(m * 4);
+    uint32_t* kbuf[2] = {(uint32_t*)take(m * 4), (uint32_t*)take(m * 4)};
+    uint32_t* vbuf[2] = {(uint32_t*)take(m * 4), (uint32_t*)take(m * 4)};
+    uint32_t* hist = (uint32_t*)take(256 * rt * 4);
+    uint32_t* stmp = (uint32_t*)take((int64_t)shd_scan_tmp_words(256 * rt) * 4);
+    int64_t* scol = (int64_t*)take((int64_t)D->n_cols * m * 8);
+    uint64_t* sseg = (uint64_t*)take(m * 8);
+    uint64_t* pk = (uint64_t*)take(m * 8);
+    int64_t* fin = (int64_t*)take((int64_t)D->n_cols * m * 16);
+    const unsigned g = (unsigned)((m + SHA_TPB - 1) / SHA_TPB);
+    hipLaunchKernelGGL(k_shc_prep, dim3(g), dim3(SHA_TPB), 0, st, d_seq, m, d_query, d_rowkey, d_keys, seq_base, klo,
+                       khi, idx);
+    if (sha_ok()) return -3;
+    int kbits = 0, qbits = 0;
+    while (kbits < 32 && ((int64_t)1 << kbits) < (int64_t)(n_keys < 1 ? 1 : n_keys)) kbits++;
+    while (qbits < 32 && ((int64_t)1 << qbits) < (int64_t)(n_query < 1 ? 1 : n_query)) qbits++;
+    if (!d_rowkey && !d_keys) kbits = 0;
+    if (!d_query) qbits = 0;
+    const uint32_t* sidx = idx;
+    if (kbits > 0) {
+        const uint32_t* ko = nullptr;
+        if (shd_sort_pairs(klo, idx, m, kbits, kbuf, vbuf, hist, stmp, stream, &ko, &sidx)) return -3;
+    }
+    if (qbits > 0) {
+        // (idx is free once the first stage has read it, and is the order itself when
+        // that stage did not run)
+        uint32_t* gv = idx;
+        hipLaunchKernelGGL(k_shc_pick, dim3(g), dim3(SHA_TPB), 0, st, (const uint32_t*)khi, sidx, m, gk, gv);
+        if (sha_ok()) return -3;
+        const uint32_t* ko = nullptr;
+        if (shd_sort_pairs(gk, gv, m, qbits, kbuf, vbuf, hist, stmp, stream, &ko, &sidx)) return -3;
+    }
+    shq_table none;
+    memset(&none, 0, sizeof(none));
+    hipLaunchKernelGGL(k_shc_gather, dim3(g), dim3(SHA_TPB), 0, st, (const int64_t*)d_vals, n_out, sidx, m, *D,
+                       (const uint32_t*)klo, (const uint32_t*)khi, scol, sseg);
+    hipLaunchKernelGGL(k_shc_walk, dim3(g), dim3(SHA_TPB), 0, st, scol, (const uint64_t*)sseg, m, *D,
+                       T && T->cap > 0 ? *T : none, pk, fin);
+    hipLaunchKernelGGL(k_sha_scatter, dim3(g), dim3(SHA_TPB), 0, st, d_vals, n_out, sidx, m, *D,
+                       (const int64_t*)scol);
+    if (sha_ok()) return -3;
+    if (put_keys) *put_keys = pk;
+    if (put_state) *put_state = fin;
+    return 0;
+}
+
+extern "C" int shc_put(const shq_table* T, const uint64_t* pk, const int64_t* fin, int64_t n,
+                       unsigned long long* d_entries, int32_t* d_err, void* stream) {
+    if (n <= 0) return 0;
+    if (!T || T->cap <= 0 || (T->cap & (T->cap - 1)) || !T->keys || !T->state || !pk || !fin || !d_entries || !d_err)
+        return -1;
+    hipLaunchKernelGGL(k_shc_put, dim3((unsigned)((n + SHA_TPB - 1) / SHA_TPB)), dim3(SHA_TPB), 0,
+                       (hipStream_t)stream, *T, pk, fin, n, d_entries, d_err);
+    return sha_ok();
 }

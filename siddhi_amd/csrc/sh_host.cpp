@@ -714,6 +714,11 @@ static uint64_t program_fingerprint(const sh_handle* h) {
         const uint8_t part = h->r_partitioned ? 1 : 0;
         f = fnv1a(&part, 1, f);
         for (const auto& t : h->stream_types) f = fnv1a(t.data(), t.size() * sizeof(int32_t), f);
+        // an aggregating set: its aggregate layout too (the carried states' columns)
+        if (h->r_aggp) {
+            f = fnv1a(h->r_agg, sizeof(h->r_agg), f);
+            f = fnv1a(h->r_argt, sizeof(h->r_argt), f);
+        }
         return f;
     }
     f = fnv1a(&h->prog, sizeof(h->prog), f);
@@ -850,6 +855,10 @@ void sh_destroy(sh_handle* h) {
             for (auto& c : R.col) c.release();
         }
         h->rc_klast.release();
+        h->ag_keys.release();
+        h->ag_state.release();
+        h->ag_ctl.release();
+        h->rc_okey.release();
         h->rc_ws.release();
         h->rc_oq.release();
         h->rc_ots.release();
@@ -881,9 +890,6 @@ static int push_impl(sh_handle* h, const sh_batch* b, const uint32_t* index, int
     if (h->mode == 2) {
         // one send(Event[]) call of a streaming rule set: staged; the device step runs
         // at the next flush, or here once kRuleStageCap events wait
-        if (h->r_aggp)
-            return fail(h, SH_E_UNSUPPORTED, "aggregating rule sets larger than the general engine's query table "
-                                             "run through sh_run_device only (no carried aggregates)");
         if (index) return fail(h, SH_E_INVALID_ARG, "sh_push_batch_part needs sh_set_coordinator first");
         if (b->stream != 0) return fail(h, SH_E_INVALID_ARG, "bad stream index");
         if (b->n <= 0) return SH_OK;
@@ -1398,9 +1404,8 @@ static int run_device_impl(sh_handle* h, sh_device_run* run) {
         // the aggregates would round in parallel: the general engine adds in sequence
         run->d_out_query = user_q;
         run->d_out_seq = user_seq;
-        if (h->mode == 2)
-            return fail(h, SH_E_UNSUPPORTED, "rule set aggregates are not exact in parallel and the set is "
-                                             "beyond the general engine's query table");
+        // (a set beyond the general engine's table never asks: its sequential pass ran, status 6)
+        if (h->mode == 2) return fail(h, SH_E_HIP, "rule engine: no sequential aggregate pass ran");
         rules_seq = true;
         h->rs_last = 0;  // (the rows below are the general engine's)
     }
@@ -1794,6 +1799,15 @@ int shx_rules_carry(sh_handle* h, int64_t* partials, int64_t* rows) {
     if (rows) *rows = h->rc_rows;
     return (int)std::min<int64_t>(h->rc_steps, 0x7FFFFFFF);
 }
+
+// carried aggregates of a streaming rule set: the (query, key) entries (also the
+// return value, saturated), and the table's capacity in entries
+int shx_rules_agg_carry(sh_handle* h, int64_t* entries) {
+    if (!h) return 0;
+    if (entries) *entries = h->ag_entries;
+    return (int)std::min<int64_t>(h->ag_entries, 0x7FFFFFFF);
+}
+int64_t shx_rules_agg_capacity(sh_handle* h) { return h ? h->ag_cap : 0; }
 
 // SH_HOST_PROF phase clocks of a streaming handle (ms and counts, SH_HP_N phases)
 int shx_host_profile(sh_handle* h, double* ms, int64_t* n, int cap) {

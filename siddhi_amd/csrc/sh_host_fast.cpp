@@ -72,6 +72,159 @@ int tile_shift_for(int64_t n, int32_t nkeys) {
     return shift;
 }
 
+// ---- carried aggregates of a streaming rule set (sh_agg.hip, "carried, sequential pass")
+static void agg_desc(const int32_t* agg_kind, const int32_t* arg_type, int n_out, sha_desc* D) {
+    memset(D, 0, sizeof(*D));
+    for (int o = 0; o < n_out && o < SHP_MAX_OUT && D->n_cols < SHA_MAX_COLS; o++)
+        if (agg_kind[o] != SH_AGG_NONE) {
+            D->c[D->n_cols].col = o;
+            D->c[D->n_cols].kind = agg_kind[o];
+            D->c[D->n_cols].arg_type = arg_type[o];
+            D->n_cols++;
+        }
+}
+
+int agg_carry_cols(const sh_handle* h) {
+    sha_desc D;
+    agg_desc(h->r_agg, h->r_argt, std::max(1, h->n_out), &D);
+    return D.n_cols;
+}
+
+shq_table agg_carry_table(const sh_handle* h) {
+    shq_table T;
+    memset(&T, 0, sizeof(T));
+    T.keys = h->ag_keys.as<uint64_t>();
+    T.state = h->ag_state.as<int64_t>();
+    T.cap = h->ag_cap;
+    T.n_cols = h->ag_ncols;
+    return T;
+}
+
+// room for `add` more entries at no more than half full: the table is rebuilt at
+// (at least) double capacity, every entry kept -- the one place a step costs O(table)
+int agg_carry_reserve(sh_handle* h, int64_t add, int n_cols) {
+    hipStream_t st = h->stream;
+    if (h->ag_ctl.ensure_fresh(64)) return SH_E_OOM;
+    const int64_t need = (h->ag_entries + add) * 2;
+    if (h->ag_cap > 0 && need <= h->ag_cap && h->ag_ncols == n_cols) return SH_OK;
+    int64_t cap = std::max<int64_t>(1024, h->ag_cap * 2);
+    while (cap < need) cap *= 2;
+    DevBuf nk, nst;
+    if (nk.ensure_fresh((size_t)cap * 8) || nst.ensure_fresh((size_t)cap * n_cols * 16)) {
+        nk.release();
+        nst.release();
+        return SH_E_OOM;
+    }
+    hipMemsetAsync(nk.p, 0xFF, (size_t)cap * 8, st);  // SHQ_EMPTY
+    hipMemsetAsync(h->ag_ctl.p, 0, 16, st);
+    int rc = 0;
+    if (h->ag_cap > 0 && h->ag_entries > 0) {
+        shq_table T;
+        memset(&T, 0, sizeof(T));
+        T.keys = nk.as<uint64_t>();
+        T.state = nst.as<int64_t>();
+        T.cap = cap;
+        T.n_cols = n_cols;
+        rc = shc_put(&T, h->ag_keys.as<uint64_t>(), h->ag_state.as<int64_t>(), h->ag_cap,
+                     h->ag_ctl.as<unsigned long long>(), h->ag_ctl.as<int32_t>() + 2, st);
+    }
+    uint64_t ctl[2] = {0, 0};
+    hipMemcpyAsync(ctl, h->ag_ctl.p, 16, hipMemcpyDeviceToHost, st);
+    if (rc || hipStreamSynchronize(st) != hipSuccess || (ctl[1] & 1) || (int64_t)ctl[0] != h->ag_entries) {
+        nk.release();
+        nst.release();
+        return SH_E_HIP;
+    }
+    h->ag_keys.release();
+    h->ag_state.release();
+    h->ag_keys = nk;
+    h->ag_state = nst;
+    h->ag_cap = cap;
+    h->ag_ncols = n_cols;
+    return SH_OK;
+}
+
+// the table emptied and filled with n entries (restore; n = 0: a fresh handle's)
+int agg_carry_load(sh_handle* h, const uint64_t* keys, const int64_t* state, int64_t n) {
+    hipStream_t st = h->stream;
+    const int nc = agg_carry_cols(h);
+    h->ag_entries = 0;
+    if (h->ag_cap > 0) hipMemsetAsync(h->ag_keys.p, 0xFF, (size_t)h->ag_cap * 8, st);
+    if (h->ag_ctl.p) hipMemsetAsync(h->ag_ctl.p, 0, 16, st);
+    if (n <= 0) return hipStreamSynchronize(st) == hipSuccess ? SH_OK : SH_E_HIP;
+    if (nc < 1) return SH_E_INVALID_ARG;
+    if (agg_carry_reserve(h, n, nc)) return SH_E_OOM;
+    DevBuf dk, ds;
+    int rc = SH_OK;
+    uint64_t ctl[2] = {0, 0};
+    if (dk.ensure_fresh((size_t)n * 8) || ds.ensure_fresh((size_t)n * nc * 16)) {
+        rc = SH_E_OOM;
+    } else {
+        hipMemcpyAsync(dk.p, keys, (size_t)n * 8, hipMemcpyHostToDevice, st);
+        hipMemcpyAsync(ds.p, state, (size_t)n * nc * 16, hipMemcpyHostToDevice, st);
+        hipMemsetAsync(h->ag_ctl.p, 0, 16, st);
+        const shq_table T = agg_carry_table(h);
+        if (shc_put(&T, dk.as<uint64_t>(), ds.as<int64_t>(), n, h->ag_ctl.as<unsigned long long>(),
+                    h->ag_ctl.as<int32_t>() + 2, st))
+            rc = SH_E_HIP;
+        hipMemcpyAsync(ctl, h->ag_ctl.p, 16, hipMemcpyDeviceToHost, st);
+        if (hipStreamSynchronize(st) != hipSuccess || (ctl[1] & 1)) rc = SH_E_HIP;
+    }
+    dk.release();
+    ds.release();
+    if (rc) return rc;
+    if ((int64_t)ctl[0] != n) return SH_E_INVALID_ARG;  // (a key twice)
+    h->ag_entries = n;
+    return SH_OK;
+}
+
+// the live entries sorted by table key, each with its per-column state
+int agg_carry_dump(sh_handle* h, std::vector<uint64_t>& keys, std::vector<int64_t>& state) {
+    keys.clear();
+    state.clear();
+    if (h->ag_cap <= 0 || h->ag_entries <= 0) return SH_OK;
+    const size_t cap = (size_t)h->ag_cap, w = (size_t)h->ag_ncols * 2;
+    std::vector<uint64_t> k(cap);
+    std::vector<int64_t> s(cap * w);
+    if (hipMemcpy(k.data(), h->ag_keys.p, cap * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(s.data(), h->ag_state.p, cap * w * 8, hipMemcpyDeviceToHost) != hipSuccess)
+        return SH_E_HIP;
+    std::vector<size_t> live;
+    for (size_t i = 0; i < cap; i++)
+        if (k[i] != SHQ_EMPTY) live.push_back(i);
+    std::sort(live.begin(), live.end(), [&](size_t a, size_t b) { return k[a] < k[b]; });
+    for (size_t i : live) {
+        keys.push_back(k[i]);
+        state.insert(state.end(), s.begin() + i * w, s.begin() + (i + 1) * w);
+    }
+    return (int64_t)keys.size() == h->ag_entries ? SH_OK : SH_E_HIP;
+}
+
+// sh_run_device on a rule set beyond the general engine's table whose additions
+// would round in parallel: the sequential pass over the placed rows (left as
+// placed by sha_running), every segment from zero -- a call's state is its own
+static int agg_seq_bulk(sh_handle* h, sh_device_run* run, int32_t nkeys) {
+    const int64_t m = run->out_count;
+    const int no = std::max(1, h->n_out);
+    sha_desc D;
+    agg_desc(h->r_agg, h->r_argt, no, &D);
+    if (m >= ((int64_t)1 << 31)) return fail(h, SH_E_UNSUPPORTED, "rule engine: 2^31 or more rows");
+    if (h->a_scratch.ensure_fresh((size_t)shc_scratch_bytes(m, D.n_cols))) return fail(h, SH_E_OOM, "aggregate scratch");
+    hipEventRecord(h->ev[4], h->stream);
+    if (shc_running(run->d_out_seq, run->d_out_values, no, m, run->d_out_query, (int32_t)h->r_rules.size(), nullptr,
+                    h->partitioned ? run->d_keys : nullptr, h->partitioned ? nkeys : 1, 0, &D, nullptr,
+                    h->a_scratch.p, h->stream, nullptr, nullptr))
+        return fail(h, SH_E_HIP, "sequential aggregate pass failed");
+    hipEventRecord(h->ev[5], h->stream);
+    if (hipEventSynchronize(h->ev[5]) != hipSuccess) return fail(h, SH_E_HIP, "device error in the aggregate pass");
+    float ms = 0.f;
+    hipEventElapsedTime(&ms, h->ev[4], h->ev[5]);
+    h->times.emit_ms += ms;
+    h->times.total_ms += ms;
+    h->agg_last = 6;
+    return SH_OK;
+}
+
 // batch-compiled rule sets (sh_rules.hip) over HBM-resident columns
 
 // the records' output order -- (run, query, consuming event), stable over the
@@ -187,6 +340,9 @@ static int rules_order_place(sh_handle* h, sh_device_run* run, int64_t m, const 
     if (shr_place(dT, order, m, rec_p, rec_q, rec_r, perm, sts, dC, 0, std::max(1, h->n_out), run->d_out_seq,
                   run->d_out_query, h->step_ots, run->d_out_values, st, sts32, tlo, h->step_seqs))
         return fail(h, SH_E_HIP, "rule placement launch failed");
+    // a step of an aggregating set: the partition key of every row's consuming event
+    if (h->step_okey && shr_place_keys(order, m, rec_q, perm, run->d_keys, h->step_okey, st))
+        return fail(h, SH_E_HIP, "rule placement launch failed");
     return SH_OK;
 }
 
@@ -204,7 +360,9 @@ static int rules_finish(sh_handle* h, sh_device_run* run, int64_t m, int32_t nke
         const int arc = agg_post(h, run, nkeys, run->d_out_query, (int)h->r_rules.size(), h->r_agg, h->r_argt,
                                  std::max(1, h->n_out));
         if (arc < 0) return arc;
-        if (arc == 1) return 1;  // not exact in parallel: the caller runs the general engine
+        // not exact in parallel: the caller runs the general engine, which adds in
+        // sequence; a set beyond its query table takes the sequential pass here
+        if (arc == 1) return h->mode == 2 ? agg_seq_bulk(h, run, nkeys) : 1;
     }
     return SH_OK;
 }
@@ -511,6 +669,7 @@ static int rules_step_fail(sh_handle* h, int code, const char* msg) {
     h->rq_call = h->rq_call0;
     h->step_seqs = nullptr;
     h->step_ots = nullptr;
+    h->step_okey = nullptr;
     return fail(h, code, msg);
 }
 
@@ -626,6 +785,8 @@ int rules_step(sh_handle* h) {
         return rules_step_fail(h, SH_E_HIP, "rule scan launch failed");
     uint32_t lo = 0, lc = 0, npairs = 0, nrows = 0;
     int32_t flag = 0;
+    const uint64_t* ag_pk = nullptr;   // carried aggregates: the step's segment heads and
+    const int64_t* ag_fin = nullptr;   // their final states (shc_running)
     hipMemcpyAsync(&lo, off + (n - 1), 4, hipMemcpyDeviceToHost, st);
     hipMemcpyAsync(&lc, cnt + (n - 1), 4, hipMemcpyDeviceToHost, st);
     hipMemcpyAsync(&npairs, soff + n, 4, hipMemcpyDeviceToHost, st);
@@ -664,13 +825,34 @@ int rules_step(sh_handle* h) {
         R.d_out_query = h->rc_oq.as<int32_t>();
         R.d_out_values = h->w_ovals.as<int64_t>();
         R.out_capacity = m;
+        sha_desc AD;
+        if (h->r_aggp) {
+            // carried aggregates: the trigger keys ride along with the placement, the
+            // table has room for a new segment per row before anything reads it (a
+            // rebuild keeps every entry, so a refusal further down loses nothing)
+            agg_desc(h->r_agg, h->r_argt, no, &AD);
+            if ((sorted && h->rc_okey.ensure_fresh((size_t)m * 4)) ||
+                h->a_scratch.ensure_fresh((size_t)shc_scratch_bytes(m, AD.n_cols)) || agg_carry_reserve(h, m, AD.n_cols))
+                return rules_step_fail(h, SH_E_OOM, "carried aggregates");
+            h->step_okey = sorted ? h->rc_okey.as<int32_t>() : nullptr;
+        }
         h->step_seqs = A.seq.as<uint64_t>();
         h->step_ots = h->rc_ots.as<int64_t>();
         // (runs from the staged events' run ids, for unpartitioned sets too)
         const int prc = rules_order_place(h, &R, m, rec_p, rec_q, rec_r, perm, sts, dC, nullptr, 0, true, false);
         h->step_seqs = nullptr;
         h->step_ots = nullptr;
+        h->step_okey = nullptr;
         if (prc) return rules_step_fail(h, prc, h->err.c_str());
+        // the running values, one addition at a time from each segment's carried state
+        // (the table itself moves last, below)
+        if (h->r_aggp) {
+            const shq_table T = agg_carry_table(h);
+            if (shc_running(h->w_oseq.as<uint64_t>(), h->w_ovals.as<int64_t>(), no, m, h->rc_oq.as<int32_t>(),
+                            (int32_t)h->r_rules.size(), sorted ? h->rc_okey.as<int32_t>() : nullptr, nullptr, nkeys, 0,
+                            &AD, &T, h->a_scratch.p, st, &ag_pk, &ag_fin))
+                return rules_step_fail(h, SH_E_HIP, "carried aggregate launch failed");
+        }
     } else {
         hipEventRecord(h->ev[2], st);
     }
@@ -694,8 +876,18 @@ int rules_step(sh_handle* h) {
             hipMemcpyAsync(h->o_vals.data() + base * h->n_out, h->w_ovals.p, (size_t)m * h->n_out * 8,
                            hipMemcpyDeviceToHost, st);
     }
-    if (shr_klast_update(sts, skeys, perm, n, (uint32_t)nc, h->rc_klast.as<int64_t>(), st) ||
-        (hipEventRecord(h->ev[3], st), hipStreamSynchronize(st)) != hipSuccess) {
+    // ... and with them the segments' final aggregate states into their table
+    uint64_t ag_ctl[2] = {0, 0};  // entries, error word
+    int arc = 0;
+    if (ag_pk) {
+        const shq_table T = agg_carry_table(h);
+        // (the device counter counts this launch alone: every shc_put starts it from zero)
+        hipMemsetAsync(h->ag_ctl.p, 0, 16, st);
+        arc = shc_put(&T, ag_pk, ag_fin, m, h->ag_ctl.as<unsigned long long>(), h->ag_ctl.as<int32_t>() + 2, st);
+        hipMemcpyAsync(ag_ctl, h->ag_ctl.p, 16, hipMemcpyDeviceToHost, st);
+    }
+    if (shr_klast_update(sts, skeys, perm, n, (uint32_t)nc, h->rc_klast.as<int64_t>(), st) || arc ||
+        (hipEventRecord(h->ev[3], st), hipStreamSynchronize(st)) != hipSuccess || (ag_ctl[1] & 1)) {
         h->o_query.resize(base);
         h->o_seq.resize(base);
         h->o_ts.resize(base);
@@ -712,6 +904,8 @@ int rules_step(sh_handle* h) {
     h->rc_pairs = npairs;
     h->rc_steps++;
     h->rs_last = 0;
+    if (ag_pk) h->ag_entries += (int64_t)ag_ctl[0];  // the slots this step claimed
+    if (h->r_aggp) h->agg_last = 6;
     h->rq_ts.clear();
     h->rq_key.clear();
     h->rq_seq.clear();
@@ -1199,7 +1393,7 @@ int agg_post(sh_handle* h, sh_device_run* run, int32_t nkeys, const int32_t* d_q
                                h->a_scratch.p, h->stream);
     if (rc < 0) return fail(h, SH_E_HIP, "aggregate post-pass failed");
     hipEventRecord(h->ev[5], h->stream);
-    hipEventSynchronize(h->ev[5]);
+    if (hipEventSynchronize(h->ev[5]) != hipSuccess) return fail(h, SH_E_HIP, "aggregate post-pass failed");
     float ms = 0.f;
     hipEventElapsedTime(&ms, h->ev[4], h->ev[5]);
     h->times.emit_ms += ms;

@@ -23,6 +23,7 @@
 
 #include "../../include/siddhi_hip.h"
 #include "sh_agg.h"
+#include "sh_agg_seq.h"
 #include "sh_device.h"
 #include "sh_jit.h"
 #include "sh_jmap.h"
@@ -351,6 +352,15 @@ struct sh_handle {
     DevBuf rc_ws, rc_oq, rc_ots;         // step workspace; placed query ids and timestamps
     const uint64_t* step_seqs = nullptr; // rules_order_place: the events' own sequence numbers (a step)
     int64_t* step_ots = nullptr;         // ... and where the rows' timestamps go
+    int32_t* step_okey = nullptr;        // ... and the partition keys of their consuming events
+    // carried aggregates of an aggregating set (sh_agg.hip shc_*): per (query, key)
+    // that ever produced a row, per aggregate column, the running sum and count, in
+    // an open-addressing table kept at most half full; ag_ctl: the slots one
+    // k_shc_put launch claimed (8 bytes, zeroed before every launch; ag_entries is
+    // the host's sum of them) and its error word
+    DevBuf ag_keys, ag_state, ag_ctl, rc_okey;
+    int64_t ag_cap = 0, ag_entries = 0;
+    int32_t ag_ncols = 0;
     // ---- bucketed window engine (sh_bucket.hip + shb_match): 0 untried, 1 loaded, <0 unavailable
     int bk_state = 0;
     int32_t part_attr0 = -1;  // stream-0 attribute keying query 0's partition
@@ -377,7 +387,8 @@ struct sh_handle {
     // numbers when the caller wants none, and the last run's path
     DevBuf a_scratch, a_seq;
     int agg_last = 0;  // 1: post-pass done, 2: post-pass not exact -> sequential engine, 3: in the k_seq3s lanes,
-                       // 4: carried per key by the bucketed engine (k_bk_aggc), 5: ... in parallel (k_bk_aggp)
+                       // 4: carried per key by the bucketed engine (k_bk_aggc), 5: ... in parallel (k_bk_aggp),
+                       // 6: carried sequential pass (k_shc_walk: a rule set beyond the general engine's table)
     std::vector<int32_t> out_types;  // per select position over the queries (-2: types differ)
     uint64_t fp = 0;                 // compiled-program fingerprint (snapshot images)
 };
@@ -434,6 +445,9 @@ int nf_upload_table(sh_handle* h);
 // sh_host_fast.cpp
 int agg_post(sh_handle* h, sh_device_run* run, int32_t nkeys, const int32_t* d_query, int n_query,
              const int32_t* agg_kind, const int32_t* arg_type, int n_out);
+int agg_carry_cols(const sh_handle* h);
+int agg_carry_dump(sh_handle* h, std::vector<uint64_t>& keys, std::vector<int64_t>& state);
+int agg_carry_load(sh_handle* h, const uint64_t* keys, const int64_t* state, int64_t n);
 int bits_for(uint64_t v);
 int carry_setup(sh_handle* h, const sh_device_run* run, shd_payload* carry, void** mid, int* alias,
                 bool used_only = false, bool with_ts = true);
@@ -458,6 +472,8 @@ int shx_seq3_status(sh_handle* h);
 int shx_agg_status(sh_handle* h);
 int shx_rules_status(sh_handle* h);
 int shx_rules_carry(sh_handle* h, int64_t* partials, int64_t* rows);
+int shx_rules_agg_carry(sh_handle* h, int64_t* entries);
+int64_t shx_rules_agg_capacity(sh_handle* h);
 int shx_host_profile(sh_handle* h, double* ms, int64_t* n, int cap);
 int shx_seq3_shape(sh_handle* h);
 int shx_bucket_compile(sh_handle* h, char* buf, int64_t len);

@@ -151,8 +151,6 @@ void get_jmap(SnapR& r, ShJMap& M) {
 }  // namespace
 
 static int snapshot_image(sh_handle* h, SnapW& w) {
-    if (h->mode == 2 && h->r_aggp)
-        return fail(h, SH_E_UNSUPPORTED, "snapshot: aggregating rule sets run through sh_run_device only");
     int rc = flush(h);  // pending send()s are processed first
     if (rc) return rc;
     if (h->has_device && hipStreamSynchronize(h->stream) != hipSuccess) return fail(h, SH_E_HIP, "snapshot sync");
@@ -205,6 +203,16 @@ static int snapshot_image(sh_handle* h, SnapW& w) {
         w.dev(A.c_off, nr ? (nr + 1) * 4 : 0);
         w.dev(A.c_rule, np * 4);
         w.dev(h->rc_klast, (size_t)h->rc_nkeys * 8);
+        if (h->r_aggp) {
+            // an aggregating set: the carried (query, key) entries sorted by table key,
+            // each with its per-column (sum, count) -- equal states, equal images
+            std::vector<uint64_t> ak;
+            std::vector<int64_t> as;
+            if (agg_carry_dump(h, ak, as)) w.bad = true;
+            w.put<int32_t>(agg_carry_cols(h));
+            w.vec(ak);
+            w.vec(as);
+        }
     } else if (h->mode == 0) {
         w.put(h->lay);
         w.put(h->nkeys_alloc);
@@ -356,6 +364,17 @@ static int restore_image(sh_handle* h, const void* buf, int64_t size) {
         if (!r.bad && r.dev(A.c_off) != (nr ? (nr + 1) * 4 : 0)) r.bad = true;
         if (!r.bad && r.dev(A.c_rule) != np * 4) r.bad = true;
         if (!r.bad && r.dev(h->rc_klast) != (uint64_t)h->rc_nkeys * 8) r.bad = true;
+        if (!r.bad && h->r_aggp) {
+            std::vector<uint64_t> ak;
+            std::vector<int64_t> as;
+            const int32_t nc = r.get<int32_t>();
+            r.vec(ak);
+            r.vec(as);
+            if (nc != agg_carry_cols(h) || as.size() != ak.size() * (size_t)nc * 2) r.bad = true;
+            for (size_t i = 0; i < ak.size() && !r.bad; i++)
+                if (ak[i] == SHQ_EMPTY || (i && ak[i] <= ak[i - 1])) r.bad = true;
+            if (!r.bad && agg_carry_load(h, ak.data(), as.data(), (int64_t)ak.size())) r.bad = true;
+        }
         if (r.bad) h->rc_rows = h->rc_pairs = h->rc_nkeys = 0;
     } else if (h->mode == 0 && !r.bad) {
         h->lay = r.get<shp_layout>();

@@ -113,6 +113,9 @@ int shr_place(const shr_table* dT, const uint32_t* order, int64_t m, const uint3
               const uint32_t* rec_r, const uint32_t* perm, const int64_t* sts, const shd_cols* dC, uint64_t seq_base,
               int n_out, uint64_t* out_seq, int32_t* out_query, int64_t* out_ts, int64_t* out_vals, void* stream,
               const uint32_t* sts32 = nullptr, int64_t tbase = 0, const uint64_t* seqs = nullptr);
+// the partition key of every placed row's consuming event (akeys: the arrival-order keys)
+int shr_place_keys(const uint32_t* order, int64_t m, const uint32_t* rec_q, const uint32_t* perm,
+                   const int32_t* akeys, int32_t* out_key, void* stream);
 // a streaming step's next carried state (sh_rules.hip, "carried state"):
 // shr_carry_ids: lid[i] = rows with survivors before row i inside its workgroup of
 // shr_carry_blocks(n) workgroups, blk[b] = such rows of workgroup b;

@@ -722,6 +722,25 @@ extern "C" int shr_place(const shr_table* dT, const uint32_t* order, int64_t m, 
     return rules_ok();
 }
 
+// a step of an aggregating set: the key each row's aggregates are kept under
+__global__ void k_rules_place_keys(const uint32_t* __restrict__ order, int64_t m, const uint32_t* __restrict__ rec_q,
+                                   const uint32_t* __restrict__ perm, const int32_t* __restrict__ akeys,
+                                   int32_t* __restrict__ out_key) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
+        const uint32_t q = rec_q[order ? order[i] : (uint32_t)i];
+        out_key[i] = akeys[perm ? perm[q] : q];
+    }
+}
+
+extern "C" int shr_place_keys(const uint32_t* order, int64_t m, const uint32_t* rec_q, const uint32_t* perm,
+                              const int32_t* akeys, int32_t* out_key, void* stream) {
+    if (m <= 0) return 0;
+    if (!akeys || !out_key) return 1;
+    hipLaunchKernelGGL(k_rules_place_keys, dim3(rgrid(m)), dim3(RTPB), 0, (hipStream_t)stream, order, m, rec_q, perm,
+                       akeys, out_key);
+    return rules_ok();
+}
+
 // the timestamps' range (min, max) of a run, for the 32-bit offsets
 __global__ void __launch_bounds__(256) k_ts_range(const int64_t* __restrict__ ts, int64_t n,
                                                   unsigned long long* __restrict__ mm) {

@@ -185,7 +185,11 @@ class DeviceRunner:
 
     def agg_status(self):
         """aggregators of the last run: 1 post-pass over a fast engine's rows
-        (sh_agg.hip), 2 not exact in parallel (a sequential engine ran), 0 none."""
+        (sh_agg.hip), 2 not exact in parallel (a sequential engine ran), 3 in the
+        rise-and-fall kernel's lanes, 4 / 5 carried by the bucketed engine
+        (sequentially / in parallel), 6 the carried sequential pass of a rule set
+        beyond the general engine's query table (sh_agg.hip k_shc_walk: every
+        streaming step, and a bulk run whose additions would round), 0 none."""
         return lib().shx_agg_status(self.handle.h)
 
     def last_error(self):
