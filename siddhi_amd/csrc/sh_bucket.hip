@@ -53,6 +53,11 @@ __device__ __forceinline__ int bk_tile(int nt) {
     return t < nt ? t : -1;
 }
 static inline unsigned bk_grid(int nt) { return 8u * (unsigned)((nt + 7) >> 3); }
+// the same order over the tiles [t0, t1) of one launch (grid: bk_grid(t1 - t0))
+__device__ __forceinline__ int bk_tile(int t0, int t1) {
+    const int t = bk_tile(t1 - t0);
+    return t < 0 ? -1 : t0 + t;
+}
 
 
 // ---------------------------------------------------------------- partition
@@ -334,7 +339,7 @@ __global__ void __launch_bounds__(BK_TPB, BK_OCC) k_bk_emit(shb_plan P, shb_out 
     __shared__ const void* o_src[SHB_MAX_OUT];
     __shared__ uint32_t s_tb;
     constexpr int NV = NO > 0 ? NO : 1;
-    const int T = bk_tile(P.nt);
+    const int T = bk_tile(P.et0, P.et1);
     if (T < 0) return;
     const int64_t b0 = (int64_t)T << SHB_TILE_SHIFT;
     const int tile_n = (int)((P.n - b0) < SHB_TILE ? (P.n - b0) : SHB_TILE);
@@ -1502,6 +1507,41 @@ extern "C" int shb_finish(shb_plan* P, uint32_t* scan_tmp, void* stream) {
     return shd_exclusive_scan(P->ttot, P->ttot, (int64_t)P->nt + 1, scan_tmp, stream);
 }
 
+// One segment of a step cut in time (run_bucket's pipeline): the exclusive scan of
+// ttot[t0, t1) in place by one workgroup, each thread a contiguous run of tiles,
+// started at *carry (the matches of the tiles before t0), which takes the
+// segment's total; the last segment writes ttot[nt]. Matchers of later segments
+// add to entries >= t1 meanwhile: other words.
+#define BK_SEG_TPB 1024
+__global__ void __launch_bounds__(BK_SEG_TPB) k_bk_scan_seg(uint32_t* __restrict__ ttot, int32_t t0, int32_t t1,
+                                                            int32_t nt, uint32_t* __restrict__ carry, int32_t last) {
+    __shared__ uint32_t ws[BK_SEG_TPB / 64];
+    const int per = (t1 - t0 + BK_SEG_TPB - 1) / BK_SEG_TPB;
+    const int a = t0 + (int)threadIdx.x * per, e = a + per < t1 ? a + per : t1;
+    uint32_t s = 0;
+    for (int t = a; t < e; t++) s += ttot[t];
+    uint32_t tot;
+    uint32_t off = shw_block_excl<BK_SEG_TPB>(s, ws, &tot) + *carry;
+    for (int t = a; t < e; t++) {
+        const uint32_t v = ttot[t];
+        ttot[t] = off;
+        off += v;
+    }
+    __syncthreads();  // (every thread has read *carry)
+    if (threadIdx.x == 0) {
+        const uint32_t c = *carry + tot;
+        *carry = c;
+        if (last) ttot[nt] = c;
+    }
+}
+
+extern "C" int shb_finish_seg(shb_plan* P, int32_t t0, int32_t t1, uint32_t* carry, int last, void* stream) {
+    if (t0 < 0 || t0 >= t1 || t1 > P->nt) return -1;
+    hipLaunchKernelGGL(k_bk_scan_seg, dim3(1), dim3(BK_SEG_TPB), 0, (hipStream_t)stream, P->ttot, t0, t1, P->nt, carry,
+                       last);
+    return bk_ok();
+}
+
 extern "C" int shb_s3_carry(const shb_plan* P, const shb_s3* S, void* stream) {
     if (P->kb > 12 || P->n_staged < 1 || P->st_width[0] != 4) return -1;
     hipLaunchKernelGGL(k_s3b, dim3(SHB_NB), dim3(S3B_TPB), 0, (hipStream_t)stream, *P, *S);
@@ -1538,7 +1578,7 @@ static void bk_emit_launch(const shb_plan* P, const shb_out* O, const shb_cols& 
     // of 7.6 (its running values by match-stream position thrash L2 harder)
     constexpr int RL = bk_ru_lm<MODE, NO>();
     if constexpr (RL > 0) {
-        hipLaunchKernelGGL((k_bk_emit<MODE, NO, RL, 6>), dim3(bk_grid(P->nt)), dim3(BK_TPB), 0, (hipStream_t)stream,
+        hipLaunchKernelGGL((k_bk_emit<MODE, NO, RL, 6>), dim3(bk_grid(P->et1 - P->et0)), dim3(BK_TPB), 0, (hipStream_t)stream,
                            *P, *O, OC, seq_base, out_seq, out_vals, out_cap);
         return;
     }
@@ -1549,7 +1589,7 @@ static void bk_emit_launch(const shb_plan* P, const shb_out* O, const shb_cols& 
                                             : (MODE == SHB_OUT_RAW ? (NO <= 6 ? 4 : 3)
                                                                    : (MODE == SHB_OUT_PACKED ? (NO <= 6 ? 4 : (NO == 7 ? 2 : 1))
                                                                                              : (NO <= 5 ? 2 : 1)));
-    hipLaunchKernelGGL((k_bk_emit<MODE, NO, RU>), dim3(bk_grid(P->nt)), dim3(BK_TPB), 0, (hipStream_t)stream, *P,
+    hipLaunchKernelGGL((k_bk_emit<MODE, NO, RU>), dim3(bk_grid(P->et1 - P->et0)), dim3(BK_TPB), 0, (hipStream_t)stream, *P,
                        *O, OC, seq_base, out_seq, out_vals, out_cap);
 }
 
@@ -1571,6 +1611,7 @@ static void bk_emit_width(const shb_plan* P, const shb_out* O, const shb_cols& O
 
 extern "C" int shb_emit(const shb_plan* P, const shb_out* O, const shb_cols* OC, uint64_t seq_base,
                         uint64_t* out_seq, int64_t* out_vals, int64_t out_cap, void* stream) {
+    if (P->et0 < 0 || P->et0 >= P->et1 || P->et1 > P->nt) return -1;
     if (OC && OC->use == SHB_OUT_PACKED) {
         if (OC->rw % 4 || OC->rw > 2 + 2 * SHB_MAX_OUT + 2) return -1;
         bk_emit_width<SHB_OUT_PACKED>(P, O, *OC, seq_base, out_seq, out_vals, out_cap, stream);

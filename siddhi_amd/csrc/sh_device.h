@@ -125,6 +125,10 @@ struct shb_plan {
     uint16_t* toff;           // [nt][SHB_TOFF]: bucket starts in the tile's bucket order ([256]: valid events)
     uint16_t* tofft;          // the same transposed, [SHB_NB + 1][tstride]: a bucket's starts over the tiles
     int32_t tstride;          // (contiguous for the matchers, which read one bucket over many tiles)
+    // one launch of a step cut into segments of whole chunks (run_bucket's pipeline;
+    // the single-launch form: c0 = 0, et0 = 0, et1 = nt)
+    int32_t c0;               // the matcher launch's first chunk (its grid: SHB_NB * the launch's chunks)
+    int32_t et0, et1;         // the emitter launch's arrival tiles [et0, et1)
     int32_t pad_t;
     // a bucket's segment lengths (toff[T][b + 1] - toff[T][b]) summed over the tiles before T,
     // in two levels: tile T's prefix = tpfx[b][T] + tpfb[b][T >> 6] (both NULL: not built)
@@ -235,6 +239,10 @@ int shd_exclusive_scan(const uint32_t* in, uint32_t* out, int64_t n, uint32_t* t
 // bucketed window engine launch steps (sh_bucket.hip), all async on `stream`
 int shb_partition(const int32_t* keys, const int64_t* ts, int32_t nkeys, shb_plan* P, void* stream);
 int shb_finish(shb_plan* P, uint32_t* scan_tmp, void* stream);
+// the same for the tiles [t0, t1) of one segment, in place, by one workgroup: *carry
+// (zeroed before the step's first segment) holds the matches of the tiles before t0
+// and takes the segment's; last: ttot[nt] <- the step's total
+int shb_finish_seg(shb_plan* P, int32_t t0, int32_t t1, uint32_t* carry, int last, void* stream);
 // the rise-and-fall sequence: one workgroup per key bucket carries its keys' state
 // across the tiles (after shb_partition with no_ts; before shb_finish)
 int shb_s3_carry(const shb_plan* P, const shb_s3* S, void* stream);

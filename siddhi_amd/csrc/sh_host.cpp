@@ -868,6 +868,9 @@ void sh_destroy(sh_handle* h) {
         }
         for (auto& e : h->ev)
             if (e) hipEventDestroy(e);
+        for (auto& e : h->bk_ev)
+            if (e) hipEventDestroy(e);
+        if (h->bk_side) hipStreamDestroy(h->bk_side);
         hipStreamDestroy(h->own_stream);
     }
     delete h->T;

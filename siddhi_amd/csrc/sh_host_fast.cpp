@@ -917,6 +917,11 @@ int rules_step(sh_handle* h) {
     return SH_OK;
 }
 
+// chunks per time segment of run_bucket's matcher / emitter pipeline (C2: 8 chunks 3.90 ms
+// per step, 16 3.70, 32 3.66-3.68 against the single launch's 3.70-3.74,
+// profiles/c2_pipeline_ab.txt)
+static constexpr int SH_BK_SEG_CHUNKS = 32;
+
 // bucketed window engine (sh_bucket.hip): partitioned window programs with a
 // consumer-side form and a null-free projection; 0 ok, 1 = not applicable or a
 // premise failed on the device (the caller runs the general window path),
@@ -1147,14 +1152,72 @@ int run_bucket(sh_handle* h, sh_device_run* run, int32_t nkeys, bool force_carry
     if (shb_partition(run->d_keys, run->d_ts, nkeys, &B, st)) return fail(h, SH_E_HIP, "bucket partition launch failed");
     hipEventRecord(h->ev[1], st);
     void* args[] = {&B};
-    if (hipModuleLaunchKernel((hipFunction_t)h->bk.match, (unsigned)(SHB_NB * B.n_chunks), 1, 1, 512, 1, 1, 0, st, args,
-                              nullptr) != hipSuccess)
-        return fail(h, SH_E_HIP, "shb_match launch failed");
-    if (carry && shb_agg_carry(&B, &AG, st)) return fail(h, SH_E_HIP, "aggregate carry launch failed");
-    if (shb_finish(&B, h->w_scan.as<uint32_t>(), st)) return fail(h, SH_E_HIP, "bucket scan launch failed");
-    hipEventRecord(h->ev[2], st);
-    if (shb_emit(&B, &O, &OC, 0, run->d_out_seq, run->d_out_values, run->out_capacity, st))
-        return fail(h, SH_E_HIP, "bucket emit launch failed");
+    B.et1 = B.nt;
+    // The matcher (VALU and LDS bound) and the emitter (parked on memory) overlap over
+    // time segments of whole chunks: the matchers of segment 0, 1, ... on the caller's
+    // stream, an event after each; behind that event, on the handle's side stream, the
+    // segment's carry scan and emitter. An emitter workgroup reads cnt, mstart and ttot
+    // of its own tile, which the matcher workgroups of that tile's chunk alone write
+    // (halo tiles are read only), and its first row: the running total the carry scan
+    // hands on. Aggregate carries, the phase clocks and steps shorter than two segments
+    // keep the single launch. SH_BK_SEG: chunks per segment (0: single launch), read per
+    // call (profiles/c2_pipeline_ab.txt)
+    int seg = SH_BK_SEG_CHUNKS;
+    if (const char* e = getenv("SH_BK_SEG")) seg = atoi(e);
+    if (seg > 0) seg = std::max(seg, (B.n_chunks + sh_handle::SH_BK_SEGS - 1) / sh_handle::SH_BK_SEGS);
+    const int n_seg = seg > 0 ? (B.n_chunks + seg - 1) / seg : 1;
+    const bool piped = !carry && !prof && (n_seg >= 2 || (seg > 0 && getenv("SH_BK_SEG")));
+    if (piped && !h->bk_side) {
+        // (created with the highest priority it lost: 3.706 against 3.682 ms per step)
+        if (hipStreamCreateWithFlags(&h->bk_side, hipStreamNonBlocking) != hipSuccess) {
+            h->bk_side = nullptr;
+            return fail(h, SH_E_HIP, "bucket side stream");
+        }
+    }
+    for (auto& e : h->bk_ev)
+        if (piped && !e && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
+            e = nullptr;
+            return fail(h, SH_E_HIP, "bucket events");
+        }
+    if (piped) {
+        hipStream_t sd = h->bk_side;
+        // (a failed launch leaves by way of both streams: the fallback engines write the
+        // same output buffers)
+        auto quit = [&](const char* what) {
+            hipStreamSynchronize(sd);
+            hipStreamSynchronize(st);
+            return fail(h, SH_E_HIP, what);
+        };
+        for (int k = 0; k < n_seg; k++) {
+            const int c0 = k * seg, c1 = std::min(c0 + seg, B.n_chunks);
+            B.c0 = c0;
+            B.et0 = c0 * B.ct;
+            B.et1 = std::min(c1 * B.ct, B.nt);
+            if (hipModuleLaunchKernel((hipFunction_t)h->bk.match, (unsigned)(SHB_NB * (c1 - c0)), 1, 1, 512, 1, 1, 0, st,
+                                      args, nullptr) != hipSuccess)
+                return quit("shb_match launch failed");
+            if (hipEventRecord(h->bk_ev[k], st) != hipSuccess || hipStreamWaitEvent(sd, h->bk_ev[k], 0) != hipSuccess)
+                return quit("bucket segment event");
+            if (shb_finish_seg(&B, B.et0, B.et1, B.ms_ctr + 2, k == n_seg - 1, sd)) return quit("bucket scan launch failed");
+            if (shb_emit(&B, &O, &OC, 0, run->d_out_seq, run->d_out_values, run->out_capacity, sd))
+                return quit("bucket emit launch failed");
+        }
+        // advance_ms: the matchers (and what of the emitters ran beside them); emit_ms:
+        // the emitters' tail after the last matcher segment
+        hipEventRecord(h->ev[2], st);
+        if (hipEventRecord(h->bk_ev[sh_handle::SH_BK_SEGS], sd) != hipSuccess ||
+            hipStreamWaitEvent(st, h->bk_ev[sh_handle::SH_BK_SEGS], 0) != hipSuccess)
+            return quit("bucket join event");
+    } else {
+        if (hipModuleLaunchKernel((hipFunction_t)h->bk.match, (unsigned)(SHB_NB * B.n_chunks), 1, 1, 512, 1, 1, 0, st,
+                                  args, nullptr) != hipSuccess)
+            return fail(h, SH_E_HIP, "shb_match launch failed");
+        if (carry && shb_agg_carry(&B, &AG, st)) return fail(h, SH_E_HIP, "aggregate carry launch failed");
+        if (shb_finish(&B, h->w_scan.as<uint32_t>(), st)) return fail(h, SH_E_HIP, "bucket scan launch failed");
+        hipEventRecord(h->ev[2], st);
+        if (shb_emit(&B, &O, &OC, 0, run->d_out_seq, run->d_out_values, run->out_capacity, st))
+            return fail(h, SH_E_HIP, "bucket emit launch failed");
+    }
     hipEventRecord(h->ev[3], st);
     hipMemcpyAsync(h->bk_rd.as<void>(0), B.flag, 4, hipMemcpyDeviceToHost, st);
     hipMemcpyAsync(h->bk_rd.as<void>(8), B.ttot + B.nt, 4, hipMemcpyDeviceToHost, st);
@@ -1251,6 +1314,7 @@ int run_s3b(sh_handle* h, sh_device_run* run, int32_t nkeys) {
     memset(&B, 0, sizeof(B));
     B.n = run->n;
     B.nt = (int32_t)((run->n + SHB_TILE - 1) / SHB_TILE);
+    B.et1 = B.nt;
     B.kb = kb;
     B.no_ts = 1;
     const int64_t slots = (int64_t)B.nt * SHB_TILE;

@@ -372,6 +372,11 @@ struct sh_handle {
     DevBuf bk_st[SHB_MAX_STAGED], bk_ms[SHB_MAX_MS], bk_agg[SHB_MAX_AGG];
     bool bk_agg_carried = false;  // the last bucketed run carried its aggregates (k_bk_aggc)
     PinBuf bk_rd;
+    // run_bucket's pipeline over time segments: the emitters' stream and one event per
+    // matcher segment ([SH_BK_SEGS]: the emitters' end), made by the first segmented run
+    static constexpr int SH_BK_SEGS = 64;
+    hipStream_t bk_side = nullptr;
+    hipEvent_t bk_ev[SH_BK_SEGS + 1] = {};
     bool aggp_refused = false;  // run_bucket: k_bk_aggp refused a value once: the post-pass from then on
     bool aggp_only = false;  // run_bucket: k_bk_aggp or nothing (1), the caller's layout kept
     // typed output columns (sh_device_run.d_out_cols) for engines that write rows

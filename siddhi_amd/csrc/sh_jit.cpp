@@ -1074,8 +1074,12 @@ __shared__ int s_i[2];
     src += R"(
 // consecutive buckets on one XCD (blocks are dealt round-robin to the 8 XCDs):
 // neighbouring segments of a tile share cache lines
-const int b = (int)((blockIdx.x & 7u) * (SHB_NB / 8) + ((blockIdx.x >> 3) & (SHB_NB / 8 - 1)));
-const int A = (int)(blockIdx.x / SHB_NB) * P.ct;
+// (the launch holds the chunks from P.c0 on: every global quantity goes by the chunk's
+// index in the step, none by the grid; SHB_NB is a multiple of 8, so the XCD of a
+// block is that of its position in the launch)
+const uint32_t gbid = (uint32_t)P.c0 * SHB_NB + blockIdx.x;
+const int b = (int)((gbid & 7u) * (SHB_NB / 8) + ((gbid >> 3) & (SHB_NB / 8 - 1)));
+const int A = (int)(gbid / SHB_NB) * P.ct;
 const int E = A + P.ct < P.nt ? A + P.ct : P.nt;
 const int kb = P.kb;
 const uint32_t kmask = (1u << kb) - 1u;
@@ -1282,8 +1286,8 @@ uint32_t total;
 // pass takes at most SHB_SPANJ), taken from the shared tail for any further one
 if (a != A && threadIdx.x == 0) s_i[1] = total ? (int)atomicAdd(P.ms_ctr, total) : 0;
 __syncthreads();
-const int64_t rbase = a == A ? (int64_t)blockIdx.x * SHB_SPAN
-                             : (int64_t)gridDim.x * SHB_SPAN + (int64_t)(uint32_t)s_i[1];
+const int64_t rbase = a == A ? (int64_t)gbid * SHB_SPAN
+                             : (int64_t)SHB_NB * P.n_chunks * SHB_SPAN + (int64_t)(uint32_t)s_i[1];
 // per chunk tile: the first match position of its segment, its matches
 for (int t = ta + (int)threadIdx.x; t < se; t += SHB_TPB) {
     const uint32_t x0 = seg_p[t] - pa, x1 = seg_p[t + 1] - pa;
