@@ -874,8 +874,11 @@ extern "C" int shd_segment_payload(const shd_batch* b, int32_t nkeys, shd_segmen
         *skeys_out = ws->keys_a;
         return hipGetLastError() == hipSuccess ? 0 : -3;
     }
-    // 17..20-bit key ranges: two passes of 10-bit digits instead of three of 8 (opt-in)
-    const int db = (bits > 16 && bits <= 20 && radix10()) ? 10 : 8;
+    // 17..20-bit key ranges: two passes of 10-bit digits instead of three of 8 (opt-in).
+    // Not with arrival tiles of more than 2^20 events: their padding takes up to
+    // 2^(tile_shift - 12) - 1 blocks, and the callers' histogram (ensure_ws: 1024 words
+    // for each block + 256) holds 10-bit digits for at most 255 padding blocks
+    const int db = (bits > 16 && bits <= 20 && radix10() && tile_shift <= 20) ? 10 : 8;
     const int passes = b->keys ? (int)((bits + db - 1) / db) : 0;
     const uint32_t* kin = nullptr;
     const uint32_t* iin = nullptr;

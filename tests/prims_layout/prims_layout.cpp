@@ -1,0 +1,38 @@
+// prims_layout.cpp — TEST INFRASTRUCTURE: prints the size and every member offset
+// of the structures tests/device_prims.py mirrors with ctypes, one
+// "struct member offset" line each ("struct sizeof bytes" for the size).
+#include <stddef.h>
+#include <stdio.h>
+
+#include "../../siddhi_amd/csrc/sh_device.h"
+
+#define SZ(S) printf(#S " sizeof %zu\n", sizeof(S))
+#define OFF(S, M) printf(#S " " #M " %zu\n", offsetof(S, M))
+
+int main() {
+    SZ(shd_batch);
+    OFF(shd_batch, ts);
+    OFF(shd_batch, stream);
+    OFF(shd_batch, row);
+    OFF(shd_batch, keys);
+    OFF(shd_batch, row_base);
+    OFF(shd_batch, pad);
+    OFF(shd_batch, seq_base);
+    OFF(shd_batch, n);
+    SZ(shd_segment_ws);
+    OFF(shd_segment_ws, keys_a);
+    OFF(shd_segment_ws, keys_b);
+    OFF(shd_segment_ws, idx_a);
+    OFF(shd_segment_ws, idx_b);
+    OFF(shd_segment_ws, hist);
+    OFF(shd_segment_ws, scan_tmp);
+    OFF(shd_segment_ws, seg_off);
+    OFF(shd_segment_ws, cap);
+    SZ(shd_payload);
+    OFF(shd_payload, n);
+    OFF(shd_payload, pad);
+    OFF(shd_payload, src);
+    OFF(shd_payload, dst);
+    OFF(shd_payload, width);
+    return 0;
+}
