@@ -105,7 +105,8 @@ int sh_start(sh_handle* h);
    against the key's last event of an earlier step) or a batch's null mask has
    a set bit; the staged calls are then dropped, sequence numbers included, and
    the carried state is what it was before them. A set whose selects aggregate
-   (sum / avg / count, one aggregate layout for the whole set) also carries one
+   (sum / avg / count / max / min of a numeric attribute, one aggregate layout for
+   the whole set; max / min keep their argument's type) also carries one
    running state per (query, partition key) that ever produced a row, and adds
    each step's rows to it one at a time in output order, as the reference does;
    a refused step leaves these states alone too. sh_start and

@@ -1,5 +1,5 @@
-// sh_agg.h — running sum / avg / count over an ordered match stream (sh_agg.hip),
-// behind the fast engines.
+// sh_agg.h — running sum / avg / count / max / min over an ordered match stream
+// (sh_agg.hip), behind the fast engines.
 #pragma once
 #include <stdint.h>
 
@@ -8,7 +8,7 @@
 // one aggregate output column of the raw rows
 struct sha_col {
     int32_t col;       // row position
-    int32_t kind;      // SH_AGG_SUM / SH_AGG_AVG / SH_AGG_COUNT
+    int32_t kind;      // SH_AGG_SUM / SH_AGG_AVG / SH_AGG_COUNT / SH_AGG_MAX / SH_AGG_MIN
     int32_t arg_type;  // argument type (the raw value the engine wrote there)
     int32_t pad;
 };
@@ -26,7 +26,8 @@ int64_t sha_scratch_bytes(int64_t m, int n_cols);
 // d_query the emitting query or NULL): each listed column's argument values
 // become the running aggregate per (query, partition key of the trigger event
 // = d_keys[seq - seq_base], NULL: one key). 0: done; 1: the double additions
-// would round (or NaN / infinite addends): the rows are as they were, run the
+// would round (or NaN / infinite addends; never for a max / min column, whose value
+// is the winning argument's raw bits): the rows are as they were, run the
 // query sequentially (sh_agg_seq.h shc_running, or a sequential engine); < 0:
 // error. On 0 the last launch (the rows' scatter) is still in flight on `stream`.
 int sha_running(const uint64_t* d_seq, int64_t* d_vals, int32_t n_out, int64_t m, const int32_t* d_query,

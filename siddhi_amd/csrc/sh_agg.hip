@@ -1,4 +1,5 @@
-// sh_agg.hip — select-clause aggregators (sum / avg / count) behind the fast engines.
+// sh_agg.hip — select-clause aggregators (sum / avg / count / max / min) behind the
+// fast engines.
 //
 // With aggregators a pattern query's selector keeps one running value per
 // partition key and query (AttributeAggregatorExecutor state through the
@@ -10,6 +11,8 @@
 //     match (SumAttributeAggregatorExecutor.java:167-185,
 //     AvgAttributeAggregatorExecutor.java:145-155: value / count)
 //   count() -> long
+//   max(x), min(x) -> x's type: the winning argument's raw bits ("max / min" below;
+//     these columns are never "not exact")
 // The fast engines (bucketed / window / rise-and-fall / rule set) write the
 // aggregator's argument in the aggregate's column; this pass turns the ordered
 // rows into the running values.
@@ -33,7 +36,9 @@
 // -> per column: k_sha_tile (segmented inclusive scan of 2,048-row tiles in
 // registers + LDS) -> k_sha_carry (one workgroup: segmented scan of the tile
 // aggregates) -> k_sha_out (carry-in, exactness check, double conversion)
-// -> k_sha_scatter (every column back into its row, one row write).
+// -> k_sha_scatter (every column back into its row, one row write). A max / min
+// column takes k_shm_tile -> k_shm_carry -> k_shm_out between the same gather and
+// scatter.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -43,6 +48,7 @@
 #include "sh_agg.h"
 #include "sh_agg_seq.h"
 #include "sh_device.h"
+#include "sh_wave.h"
 
 #define SHA_TPB 256
 #define SHA_ITEMS 8
@@ -433,6 +439,174 @@ __global__ void __launch_bounds__(SHA_TPB) k_sha_scatter(int64_t* __restrict__ v
     for (int k = 0; k < D.n_cols; k++) row[D.c[k].col] = sc[(int64_t)k * m + p];
 }
 
+// ---------------------------------------------------------------- max / min
+// max(x) / min(x) over the same sorted columns (sh_agg_seq.h shq_better restates the
+// reference). In sequence the rule is not associative over raw floats (a NaN
+// argument never replaces, a NaN state is never replaced), so the scan element
+// encodes it: a NaN argument is the identity (no value), a NaN at a segment head is
+// absorbing (the segment's first argument: every row of the segment is that NaN),
+// and of two values that compare equal the left one stays (-0.0 / +0.0). That is
+// "the earliest argument attaining the extreme", a segmented scan: one 64-bit
+// value (the winning argument's raw bits) plus three flag bits.
+#define SHM_HEAD 1u  // a segment starts inside the span
+#define SHM_HAS 2u   // the span (since its last start) holds a value
+#define SHM_ABS 4u   // ... started with a NaN: v is that NaN, nothing replaces it
+
+struct shm_el {
+    uint64_t v;
+    uint32_t f;
+};
+
+__device__ __forceinline__ shm_el shm_comb(const shm_el& a, const shm_el& b, const sha_col& c) {
+    if (b.f & SHM_HEAD) return b;
+    shm_el r = a;
+    if ((a.f & SHM_ABS) || !(b.f & SHM_HAS)) return r;
+    if (!(a.f & SHM_HAS) || shq_better(c.kind, c.arg_type, (int64_t)b.v, (int64_t)a.v)) {
+        r.v = b.v;
+        r.f = a.f | SHM_HAS;
+    }
+    return r;
+}
+
+template <int CTRL>
+__device__ __forceinline__ shm_el shm_move(const shm_el& a) {
+    shm_el r;
+    r.v = shw_move64<CTRL>(a.v);
+    r.f = shw_move<CTRL>(a.f);
+    return r;
+}
+
+// inclusive scan over the 64 lanes of a wave: the DPP row shifts and row
+// broadcasts of sh_wave.h with shm_comb in place of the addition (a lane without a
+// source is guarded, as there)
+__device__ __forceinline__ shm_el shm_wave_scan(shm_el x, const sha_col& c) {
+    const int lane = threadIdx.x & 63, rl = lane & 15;
+    shm_el t;
+    t = shm_move<SHW_ROW_SHR(1)>(x);
+    if (rl >= 1) x = shm_comb(t, x, c);
+    t = shm_move<SHW_ROW_SHR(2)>(x);
+    if (rl >= 2) x = shm_comb(t, x, c);
+    t = shm_move<SHW_ROW_SHR(4)>(x);
+    if (rl >= 4) x = shm_comb(t, x, c);
+    t = shm_move<SHW_ROW_SHR(8)>(x);
+    if (rl >= 8) x = shm_comb(t, x, c);
+    t = shm_move<SHW_ROW_BCAST15>(x);
+    if ((lane & 31) >= 16) x = shm_comb(t, x, c);
+    t = shm_move<SHW_ROW_BCAST31>(x);
+    if (lane >= 32) x = shm_comb(t, x, c);
+    return x;
+}
+
+// workgroup scan of one element per thread: *inc the inclusive value, the return
+// value the exclusive one (the identity for thread 0); wsum: one element per wave
+template <int NT>
+__device__ __forceinline__ shm_el shm_block_scan(const shm_el& x, const sha_col& c, shm_el* wsum, shm_el* inc) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const shm_el wi = shm_wave_scan(x, c);
+    if (lane == 63) wsum[w] = wi;
+    __syncthreads();
+    shm_el pre;  // the waves before this one
+    pre.v = 0ull;
+    pre.f = 0u;
+    for (int i = 0; i < w; i++) pre = shm_comb(pre, wsum[i], c);
+    // the lane below's inclusive value (lane 0: none)
+    shm_el up;
+    up.v = (uint64_t)__shfl_up((long long)wi.v, 1, 64);
+    up.f = (uint32_t)__shfl_up((int)wi.f, 1, 64);
+    if (lane == 0) {
+        up.v = 0ull;
+        up.f = 0u;
+    }
+    __syncthreads();
+    *inc = shm_comb(pre, wi, c);
+    return shm_comb(pre, up, c);
+}
+
+// per tile, in place: the column's arguments become the inclusive segmented scan's
+// values (sorted order), has[p] whether the span from the tile's start to p holds
+// a value; the tile's aggregate and the offset of its first segment start
+__global__ void __launch_bounds__(SHA_TPB) k_shm_tile(int64_t* __restrict__ scol, const uint32_t* __restrict__ sseg,
+                                                      int64_t m, sha_col c, uint8_t* __restrict__ has,
+                                                      shm_el* __restrict__ tiles, uint32_t* __restrict__ first_head) {
+    __shared__ shm_el wsum[SHA_TPB / 64];
+    __shared__ uint32_t fh;
+    const int64_t t0 = (int64_t)blockIdx.x * SHA_TILE;
+    const int64_t p0 = t0 + (int64_t)threadIdx.x * SHA_ITEMS;
+    if (threadIdx.x == 0) fh = SHA_TILE;
+    __syncthreads();
+    shm_el it[SHA_ITEMS];
+    shm_el acc;
+    acc.v = 0ull;
+    acc.f = 0u;
+    uint32_t myfh = SHA_TILE;
+#pragma unroll
+    for (int j = 0; j < SHA_ITEMS; j++) {
+        const int64_t p = p0 + j;
+        shm_el x;
+        x.v = 0ull;
+        x.f = 0u;
+        if (p < m) {
+            x.v = (uint64_t)scol[p];
+            const bool head = p == 0 || sseg[p] != sseg[p - 1];
+            const bool nan = shq_arg_nan((int64_t)x.v, c.arg_type);
+            x.f = (head ? SHM_HEAD : 0u) | (nan ? (head ? SHM_ABS : 0u) : SHM_HAS);
+            if (head && myfh == SHA_TILE) myfh = (uint32_t)(p - t0);
+        }
+        acc = j == 0 ? x : shm_comb(acc, x, c);
+        it[j] = acc;
+    }
+    if (myfh != SHA_TILE) atomicMin(&fh, myfh);
+    shm_el inc;
+    const shm_el pre = shm_block_scan<SHA_TPB>(acc, c, wsum, &inc);
+#pragma unroll
+    for (int j = 0; j < SHA_ITEMS; j++) {
+        const int64_t p = p0 + j;
+        if (p >= m) break;
+        const shm_el y = shm_comb(pre, it[j], c);
+        scol[p] = (int64_t)y.v;
+        has[p] = (uint8_t)(y.f & (SHM_HAS | SHM_ABS));
+    }
+    __syncthreads();
+    if (threadIdx.x == SHA_TPB - 1) {
+        tiles[blockIdx.x] = inc;
+        first_head[blockIdx.x] = fh;
+    }
+}
+
+// exclusive segmented scan of the tile aggregates (one workgroup; a thread walks
+// its run of ceil(nt / SHA_CARRY_TPB) tiles)
+__global__ void __launch_bounds__(SHA_CARRY_TPB) k_shm_carry(shm_el* __restrict__ tiles, int64_t nt, sha_col c) {
+    __shared__ shm_el wsum[SHA_CARRY_TPB / 64];
+    const int64_t per = (nt + SHA_CARRY_TPB - 1) / SHA_CARRY_TPB;
+    const int64_t b = (int64_t)threadIdx.x * per;
+    shm_el acc;
+    acc.v = 0ull;
+    acc.f = 0u;
+    for (int64_t t = b; t < b + per && t < nt; t++) acc = shm_comb(acc, tiles[t], c);
+    shm_el inc;
+    shm_el run = shm_block_scan<SHA_CARRY_TPB>(acc, c, wsum, &inc);
+    for (int64_t t = b; t < b + per && t < nt; t++) {
+        const shm_el x = tiles[t];
+        tiles[t] = run;  // exclusive
+        run = shm_comb(run, x, c);
+    }
+}
+
+// the rows before their tile's first segment start take the carry-in (the others
+// are final as k_shm_tile left them)
+__global__ void __launch_bounds__(SHA_TPB) k_shm_out(int64_t* __restrict__ scol, int64_t m, sha_col c,
+                                                     const uint8_t* __restrict__ has, const shm_el* __restrict__ tiles,
+                                                     const uint32_t* __restrict__ first_head) {
+    const int64_t p = (int64_t)blockIdx.x * SHA_TPB + threadIdx.x;
+    if (p >= m) return;
+    const int64_t t = p / SHA_TILE;
+    if ((uint32_t)(p - t * SHA_TILE) >= first_head[t]) return;
+    shm_el x;
+    x.v = (uint64_t)scol[p];
+    x.f = has[p];
+    scol[p] = (int64_t)shm_comb(tiles[t], x, c).v;
+}
+
 // ---------------------------------------------------------------- host
 extern "C" int64_t sha_scratch_bytes(int64_t m, int n_cols) {
     const int64_t nt = (m + SHA_TILE - 1) / SHA_TILE;
@@ -510,6 +684,16 @@ extern "C" int sha_running(const uint64_t* d_seq, int64_t* d_vals, int32_t n_out
             }
         }
         int64_t* colk = scol + (int64_t)k * m;
+        if (shq_minmax(c.kind)) {
+            // never "not exact": the scan is the reference's rule itself (sc: the has bytes)
+            hipLaunchKernelGGL(k_shm_tile, dim3((unsigned)nt), dim3(SHA_TPB), 0, st, colk, sseg, m, c, (uint8_t*)sc,
+                               (shm_el*)tiles, fh);
+            hipLaunchKernelGGL(k_shm_carry, dim3(1), dim3(SHA_CARRY_TPB), 0, st, (shm_el*)tiles, nt, c);
+            hipLaunchKernelGGL(k_shm_out, dim3(g), dim3(SHA_TPB), 0, st, colk, m, c, (const uint8_t*)sc,
+                               (const shm_el*)tiles, (const uint32_t*)fh);
+            if (sha_ok()) return -3;
+            continue;
+        }
         hipLaunchKernelGGL(k_sha_tile, dim3((unsigned)nt), dim3(SHA_TPB), 0, st, (const int64_t*)colk, sseg, m, c, q,
                            sv, sc, tiles, fh);
         hipLaunchKernelGGL(k_sha_carry, dim3(1), dim3(SHA_CARRY_TPB), 0, st, tiles, nt);

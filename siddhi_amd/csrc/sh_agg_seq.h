@@ -7,6 +7,7 @@
 // sum(float|double) and avg(*) as value += (double) x, avg emitting value / count.
 // Plain double additions (built with -ffp-contract=off) round as Java's do, and
 // carry NaN and the infinities the same way, so the walk needs no exactness proof.
+// max(x) / min(x) keep the winning argument's raw bits in the sum word (shq_better).
 #pragma once
 #include <stdint.h>
 
@@ -89,11 +90,42 @@ SHQ_HD double shq_as_double(int64_t raw, int arg_type) {
     }
 }
 
-// one match into the running state (*sum: long or double bits, *cnt); returns the
-// value the row carries
+// ---- max / min (MaxAttributeAggregatorExecutor / MinAttributeAggregatorExecutor
+// processAdd): an empty state takes the argument, otherwise the argument replaces
+// the state iff state < arg (max) / state > arg (min) in the argument's own type,
+// and the row carries the state's raw bits. A NaN argument therefore never
+// replaces a value, a NaN state (the first argument ever) is never replaced, and
+// of -0.0 and +0.0 the first stays.
+SHQ_HD bool shq_minmax(int kind) { return kind == SH_AGG_MAX || kind == SH_AGG_MIN; }
+
+SHQ_HD bool shq_arg_nan(int64_t raw, int arg_type) {
+    if (arg_type != SH_T_FLOAT && arg_type != SH_T_DOUBLE) return false;
+    const double d = shq_as_double(raw, arg_type);
+    return d != d;
+}
+
+// `arg` replaces `state` (float widens to double exactly: the same IEEE ordering;
+// int and long compare as integers, never through a double)
+SHQ_HD bool shq_better(int kind, int arg_type, int64_t arg, int64_t state) {
+    if (arg_type == SH_T_FLOAT || arg_type == SH_T_DOUBLE) {
+        const double a = shq_as_double(arg, arg_type), s = shq_as_double(state, arg_type);
+        return kind == SH_AGG_MAX ? s < a : s > a;
+    }
+    const int64_t a = arg_type == SH_T_INT ? (int64_t)(int32_t)arg : arg;
+    const int64_t s = arg_type == SH_T_INT ? (int64_t)(int32_t)state : state;
+    return kind == SH_AGG_MAX ? s < a : s > a;
+}
+
+// one match into the running state (*sum: long or double bits -- for max / min the
+// winning argument's raw bits --, *cnt: the adds, 0 = empty); returns the value the
+// row carries
 SHQ_HD int64_t shq_add(int64_t* sum, int64_t* cnt, int64_t raw, int kind, int arg_type) {
     *cnt = (int64_t)((uint64_t)*cnt + 1ull);
     if (kind == SH_AGG_COUNT) return *cnt;
+    if (shq_minmax(kind)) {
+        if (*cnt == 1 || shq_better(kind, arg_type, raw, *sum)) *sum = raw;
+        return *sum;
+    }
     if (!shq_fp(kind, arg_type)) {
         const int64_t v = arg_type == SH_T_INT ? (int64_t)(int32_t)raw : raw;
         *sum = (int64_t)((uint64_t)*sum + (uint64_t)v);  // wraps like Java's long
@@ -113,6 +145,18 @@ SHQ_HD void shq_walk(int64_t* col, int64_t p0, int64_t p1, const sha_col& c, con
     if (slot >= 0) {
         sum = T.state[(slot * T.n_cols + k) * 2];
         cnt = T.state[(slot * T.n_cols + k) * 2 + 1];
+    }
+    if (shq_minmax(c.kind)) {
+        // (a loop of its own: the sums' loop keeps its registers)
+        for (int64_t p = p0; p < p1; p++) {
+            const int64_t raw = col[p];
+            if (cnt == 0 || shq_better(c.kind, c.arg_type, raw, sum)) sum = raw;
+            cnt = (int64_t)((uint64_t)cnt + 1ull);
+            col[p] = sum;
+        }
+        fin[0] = sum;
+        fin[1] = cnt;
+        return;
     }
     for (int64_t p = p0; p < p1; p++) col[p] = shq_add(&sum, &cnt, col[p], c.kind, c.arg_type);
     fin[0] = sum;

@@ -178,7 +178,7 @@ struct shb_aggc {
     int32_t n;
     int32_t e1_col, e1_type;      // match-stream column of the e1-side argument (-1: none; 4-byte)
     int32_t e2_col[2], e2_type[2];  // staged columns of e2-side arguments (-1: none; [1]: 4-byte)
-    int32_t kind[SHB_MAX_AGG];    // SH_AGG_SUM / AVG / COUNT
+    int32_t kind[SHB_MAX_AGG];    // SH_AGG_SUM / AVG / COUNT (max / min: not carried here, sh_agg.hip)
     int32_t side[SHB_MAX_AGG];    // 0: e1, 1: e2 column 0, 2: e2 column 1, 3: none
     void* out[SHB_MAX_AGG];       // [match-stream positions] int64 / double bits
     int32_t parallel;             // 1: k_bk_aggp (segmented prefix, exact fixed point), 0: k_bk_aggc

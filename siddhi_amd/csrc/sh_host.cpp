@@ -333,7 +333,12 @@ static int lower_chain(sh_handle* h, const sh_app_desc* app, int qi, shp_program
     P.agg_post = 0;
     for (int o = 0; o < q.n_outputs; o++) {
         const sh_output_attr& oa = q.outputs[o];
-        const bool postable = oa.agg == SH_AGG_SUM || oa.agg == SH_AGG_AVG || oa.agg == SH_AGG_COUNT;
+        bool postable = oa.agg == SH_AGG_SUM || oa.agg == SH_AGG_AVG || oa.agg == SH_AGG_COUNT;
+        if ((oa.agg == SH_AGG_MAX || oa.agg == SH_AGG_MIN) && oa.expr >= 0) {
+            // max / min of a numeric attribute keeps the argument's type (sh_agg.hip "max / min")
+            const int t = q.exprs[oa.expr].type;
+            postable = t == SH_T_INT || t == SH_T_LONG || t == SH_T_FLOAT || t == SH_T_DOUBLE;
+        }
         if (oa.agg == SH_AGG_COUNT && oa.expr < 0) {
             // count(): the row carries any value; the post-pass counts rows
             P.out_slot[o] = 1;

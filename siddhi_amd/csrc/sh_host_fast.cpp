@@ -932,6 +932,10 @@ int run_bucket(sh_handle* h, sh_device_run* run, int32_t nkeys, bool force_carry
     const shp_program& P = h->prog;
     const int64_t n = run->n;
     if (off || !h->partitioned || nkeys < 1024 || !P.out_fast || n < SHB_TILE) return 1;
+    // a max / min select is not offered to this engine yet: the window engine writes
+    // its arguments and the post-pass (sh_agg.hip "max / min") forms the values
+    for (int o = 0; o < P.n_out; o++)
+        if (P.out_agg[o] == SH_AGG_MAX || P.out_agg[o] == SH_AGG_MIN) return 1;
     const int kb = std::max(0, bits_for((uint64_t)(nkeys - 1)) - 8);
     if (kb > 8) return 1;
     // select list: e2-side values (and e1's partition attribute, equal to e2's

@@ -472,12 +472,19 @@ struct QueryLowering {
                 Q->s3_out_type[o] = (int8_t)app->streams[c3.stream].attr_types[0];
                 continue;
             }
-            if (oa.agg != SH_AGG_NONE && oa.agg != SH_AGG_SUM && oa.agg != SH_AGG_AVG && oa.agg != SH_AGG_COUNT) return;
+            // (max / min too: k_seq3s keeps only sum / avg / count in its lanes, so
+            // those rows always take the post-pass)
+            if (oa.agg != SH_AGG_NONE && oa.agg != SH_AGG_SUM && oa.agg != SH_AGG_AVG && oa.agg != SH_AGG_COUNT &&
+                oa.agg != SH_AGG_MAX && oa.agg != SH_AGG_MIN)
+                return;
             if (oa.expr < 0) return;
             const sh_expr& x = q->exprs[oa.expr];
             int at, ty;
             if (x.op != SH_OP_VAR || x.slot < 0 || x.slot > 2) return;
             if (!var(oa.expr, x.slot, x.slot == 1, &at, &ty)) return;
+            if ((oa.agg == SH_AGG_MAX || oa.agg == SH_AGG_MIN) && ty != SH_T_INT && ty != SH_T_LONG && ty != SH_T_FLOAT &&
+                ty != SH_T_DOUBLE)
+                return;
             Q->s3_out_slot[o] = (int8_t)x.slot;
             Q->s3_out_attr[o] = (int8_t)at;
             Q->s3_out_type[o] = (int8_t)ty;

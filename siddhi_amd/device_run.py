@@ -184,10 +184,11 @@ class DeviceRunner:
         return lib().shx_rules_status(self.handle.h)
 
     def agg_status(self):
-        """aggregators of the last run: 1 post-pass over a fast engine's rows
-        (sh_agg.hip), 2 not exact in parallel (a sequential engine ran), 3 in the
-        rise-and-fall kernel's lanes, 4 / 5 carried by the bucketed engine
-        (sequentially / in parallel), 6 the carried sequential pass of a rule set
+        """aggregators (sum / avg / count / max / min) of the last run: 1 post-pass
+        over a fast engine's rows (sh_agg.hip; every max / min select), 2 a sum / avg
+        not exact in parallel (a sequential engine ran), 3 sum / avg / count in the
+        rise-and-fall kernel's lanes, 4 / 5 sum / avg / count carried by the bucketed
+        engine (sequentially / in parallel), 6 the carried sequential pass of a rule set
         beyond the general engine's query table (sh_agg.hip k_shc_walk: every
         streaming step, and a bulk run whose additions would round), 0 none."""
         return lib().shx_agg_status(self.handle.h)
