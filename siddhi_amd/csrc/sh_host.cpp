@@ -1102,15 +1102,7 @@ static int run_batch(sh_handle* h, const shd_batch& B, int32_t nkeys, const shd_
         hipMemsetAsync(h->w_ctr.p, 0, 8, st);
         hipMemsetAsync(h->d_err.p, 0, 8, st);
         if (timed) hipEventRecord(h->ev[0], st);
-        shd_segment_ws ws;
-        ws.keys_a = h->w_keys_a.as<uint32_t>();
-        ws.keys_b = h->w_keys_b.as<uint32_t>();
-        ws.idx_a = h->w_idx_a.as<uint32_t>();
-        ws.idx_b = h->w_idx_b.as<uint32_t>();
-        ws.hist = h->w_hist.as<uint32_t>();
-        ws.scan_tmp = h->w_scan.as<uint32_t>();
-        ws.seg_off = h->w_seg.as<uint32_t>();
-        ws.cap = n;
+        shd_segment_ws ws = seg_ws(h, n);
         const uint32_t* perm = nullptr;
         const uint32_t* skeys = nullptr;
         int rc = shd_segment(&B, nkeys, &ws, st, &perm, &skeys);
@@ -1199,10 +1191,7 @@ static int run_batch(sh_handle* h, const shd_batch& B, int32_t nkeys, const shd_
         if (timed) hipEventRecord(h->ev[3], st);
         if (hipStreamSynchronize(st) != hipSuccess) return fail(h, SH_E_HIP, "device error in placement");
         if (timed) {
-            hipEventElapsedTime(&h->times.segment_ms, h->ev[0], h->ev[1]);
-            hipEventElapsedTime(&h->times.advance_ms, h->ev[1], h->ev[2]);
-            hipEventElapsedTime(&h->times.emit_ms, h->ev[2], h->ev[3]);
-            hipEventElapsedTime(&h->times.total_ms, h->ev[0], h->ev[3]);
+            phase_times(h);
             h->times.advance_launches++;
         }
         backup.release();
@@ -1393,6 +1382,177 @@ int64_t sh_list_get(sh_handle* h, int64_t list, int64_t cap, int64_t* values, ui
 }
 int sh_drain_ordered(sh_handle* h, sh_match_buf* out, uint64_t* order) { return drain_impl(h, out, order); }
 
+// ---- sh_run_device: the engine ladder (DESIGN.md "Aggregators on the fast engines").
+// A rung is an engine's function answering 0 (its rows stand), 1 (not applicable, or
+// a premise failed on the device: the next rung) or an error
+
+// the rule-set rung (sh_rules.hip); 1: a general-engine set's aggregates would round
+// in parallel, that engine adds in sequence
+static int rung_rules(sh_handle* h, sh_device_run* run) {
+    const int crc = rows_for_cols(h, run);
+    if (crc) return crc;
+    int32_t* user_q = run->d_out_query;
+    uint64_t* user_seq = run->d_out_seq;
+    const int rrc = run_rules(h, run);
+    if (rrc != 1) return rrc;
+    run->d_out_query = user_q;
+    run->d_out_seq = user_seq;
+    // (a set beyond the general engine's table never asks: its sequential pass ran, status 6)
+    if (h->mode == 2) return fail(h, SH_E_HIP, "rule engine: no sequential aggregate pass ran");
+    h->rs_last = 0;  // (the rows below are the general engine's)
+    return 1;
+}
+
+// the general-engine rung from fresh per-key state: the sequence bucket-carry engine,
+// then k_seq3 (and the post-pass of its aggregates), then k_nfa_run; the events arrive
+// as send() calls of run->batch_events. rules_seq: a rule set's aggregates left the
+// post-pass for this engine
+static int run_general(sh_handle* h, sh_device_run* run, bool rules_seq) {
+    if (h->T->has_absent) return fail(h, SH_E_UNSUPPORTED, "sh_run_device: absent states need sh_push_batch");
+    const int32_t nkeys = h->partitioned ? std::max(1, run->n_keys) : 1;
+    if (nf_ensure_keys(h, nkeys)) return fail(h, SH_E_OOM, "key state");
+    const nf_query& Q0 = h->T->q[0];
+    const bool aggp = h->T->n_queries == 1 && Q0.s3 && Q0.contains_agg;
+    if (aggp && !run->d_out_seq) {
+        if (h->a_seq.ensure((size_t)std::max<int64_t>(1, run->out_capacity) * 8))
+            return fail(h, SH_E_OOM, "aggregate sequence numbers");
+        run->d_out_seq = h->a_seq.as<uint64_t>();
+    }
+    // (the sequence bucket-carry engine writes typed columns / packed rows itself)
+    const int src = run_s3b(h, run, nkeys);
+    if (src != 1) {
+        if (src == SH_OK) h->kstate_stale = true;  // (no key blocks used: reset for a later user)
+        return src;
+    }
+    const int crc = rows_for_cols(h, run);
+    if (crc) return crc;
+    int rc = SH_OK;
+    int64_t rows = 0;
+    h->agg_last = rules_seq ? 2 : 0;
+    bool no_seq3 = false;  // the second pass: k_seq3's aggregates were not exact in parallel
+    for (int pass = 0; pass < 2; pass++) {
+        // the rise-and-fall engine keeps no key blocks: their reset waits for a
+        // later user (kstate_stale)
+        const bool s3_run = !no_seq3 && nf_takes_seq3(h);
+        if (s3_run) {
+            h->kstate_stale = true;
+        } else {
+            hipMemsetAsync(h->n_kstate.p, 0, (size_t)nkeys * h->T->key_words * 8, h->stream);
+            h->kstate_stale = false;
+        }
+        h->started = false;
+        rc = nf_start(h);
+        if (rc) return rc;
+        nf_cols cols;
+        memset(&cols, 0, sizeof(cols));  // (nf_put_cols compares the image bytewise)
+        for (size_t a = 0; a < h->stream_types[0].size(); a++) cols.col[0][a] = run->d_cols[a];
+        rows = 0;
+        h->times = sh_kernel_times{};
+        h->dev_want_query = run->d_out_query != nullptr;
+        h->dev_run_ids = run->d_run;
+        const NfOpts po{true, run->batch_events, s3_run, getenv("SH_NFA_GATHER") ? nullptr : run};
+        rc = nf_process(h, device_batch(h, run), nkeys, cols, run->d_out_seq, run->d_out_values, run->out_capacity,
+                        &rows, po);
+        h->dev_run_ids = nullptr;
+        run->out_count = rows;
+        if (rc == SH_OK && aggp && h->seq3_last && h->s3_agg) h->agg_last = 3;
+        if (rc != SH_OK || !aggp || !h->seq3_last || h->s3_agg) break;
+        // k_seq3 wrote the aggregators' arguments: the running values
+        int32_t arg_type[NF_MAX_OUT];
+        for (int o = 0; o < Q0.n_out; o++) arg_type[o] = Q0.s3_out_type[o];
+        const int arc = agg_post(h, run, nkeys, nullptr, 1, Q0.out_agg, arg_type, Q0.n_out);
+        if (arc < 0) return arc;
+        if (arc == 0) break;
+        no_seq3 = true;  // not exact: the general engine adds in sequence
+    }
+    if (rc == SH_OK && run->d_out_query && rows > 0) {
+        hipMemcpyAsync(run->d_out_query, h->w_oq.p, rows * 4, hipMemcpyDeviceToDevice, h->stream);
+        hipStreamSynchronize(h->stream);
+    }
+    return rc;
+}
+
+// the chain mode's last rung: the sequential per-key engine (sh_kernels.hip)
+static int rung_batch(sh_handle* h, sh_device_run* run, int32_t nkeys) {
+    shd_cols cols{};
+    for (size_t a = 0; a < h->stream_types[0].size(); a++) cols.col[0][a] = run->d_cols[a];
+    int64_t nm = 0;
+    const int rc = run_batch(h, device_batch(h, run), nkeys, cols, run->d_out_seq, nullptr, run->d_out_values, nullptr,
+                             run->out_capacity, &nm, true);
+    run->out_count = nm;
+    if (rc == SH_OK && run->d_out_query && nm > 0) {
+        hipMemsetAsync(run->d_out_query, 0, nm * 4, h->stream);
+        hipStreamSynchronize(h->stream);
+    }
+    return rc;
+}
+
+// the bucketed engine's aggregate modes of this call in the order to try (the next one
+// after the device refused the one before): the one place that reads SH_BK_AGG_POST,
+// SH_BK_AGGC and SH_BK_AGGP=0 (per call). after_post: the post-pass found its
+// additions not exact
+static int bucket_agg_modes(const sh_handle* h, const sh_device_run* run, bool after_post, BkAgg m[2]) {
+    const char* aggp = getenv("SH_BK_AGGP");
+    m[0] = m[1] = BK_AGG_ROWS;
+    if (getenv("SH_BK_AGG_POST")) return after_post ? 0 : 1;
+    if (after_post || getenv("SH_BK_AGGC")) m[0] = BK_AGG_SEQ;
+    else if (!(aggp && aggp[0] == '0') && !h->aggp_refused && run->n < ((int64_t)1 << 31)) m[0] = BK_AGG_PAR;
+    return m[0] == BK_AGG_PAR ? 2 : 1;
+}
+
+// the chain mode's rungs: the bucketed engine (its own writer of packed rows / typed
+// columns), the window engine, the sequential engine. agg: under a select with
+// aggregators (agg_status in brackets) the bucketed engine's carries form the running
+// values themselves, and the post-pass (sh_agg.hip) forms them from raw rows of
+// arguments, 1 when its additions would round in parallel
+static int run_chain(sh_handle* h, sh_device_run* run, int32_t nkeys) {
+    const shp_program& P = h->prog;
+    const bool agg = P.agg_post != 0;
+    auto post = [&] { return agg_post(h, run, nkeys, nullptr, 1, P.out_agg, P.out_arg_type, P.n_out); };
+    BkAgg m[2] = {BK_AGG_ROWS, BK_AGG_ROWS};
+    BkRun br;
+    int rc;
+    // 1. packed rows / typed columns straight from the bucketed engine when its
+    // parallel carry takes the batch [5], or nothing
+    if (agg && P.window_ok && h->out_mode != SHB_OUT_RAW && !h->cols_rows && bucket_agg_modes(h, run, false, m) &&
+        m[0] == BK_AGG_PAR && (rc = run_bucket(h, run, nkeys, BK_AGG_PAR, &br)) != 1)
+        return rc;
+    // 2. raw rows from here on, with sequence numbers for the post-pass
+    if (agg && (rc = rows_for_cols(h, run))) return rc;
+    if (agg && !run->d_out_seq) {
+        if (h->a_seq.ensure((size_t)std::max<int64_t>(1, run->out_capacity) * 8))
+            return fail(h, SH_E_OOM, "aggregate sequence numbers");
+        run->d_out_seq = h->a_seq.as<uint64_t>();
+    }
+    // 3. the bucketed engine, under aggregators in the first applicable mode [5 / 4] and
+    // once more in the next after the device refused the parallel carry
+    rc = 1;
+    if (P.window_ok) {
+        const int nm = agg ? bucket_agg_modes(h, run, false, m) : 1;
+        rc = run_bucket(h, run, nkeys, m[0], &br);
+        if (rc == 1 && br.refused && nm > 1) rc = run_bucket(h, run, nkeys, m[1], &br);
+    }
+    if (agg && rc == SH_OK && br.carried == BK_AGG_ROWS) {
+        // 4. it wrote the arguments: the post-pass [1]
+        if ((rc = post()) <= 0) return rc;
+        // 5. not exact [2]: the bucketed engine again, its sequential carry adding in
+        // the reference's sequence [4]
+        if (bucket_agg_modes(h, run, true, m)) {
+            rc = run_bucket(h, run, nkeys, m[0], &br);
+            if (rc == SH_OK && br.carried != BK_AGG_ROWS) return SH_OK;
+            if (rc != SH_OK && rc != 1) return rc;
+        }
+        return rung_batch(h, run, nkeys);  // [2]
+    }
+    if (rc != 1) return rc;
+    // 6. the window engine, on raw rows, and the post-pass of its rows [1]
+    if ((rc = rows_for_cols(h, run))) return rc;
+    rc = P.window_ok ? run_window(h, run, nkeys) : 1;
+    if (agg && rc == SH_OK && (rc = post()) <= 0) return rc;
+    // 7. the sequential engine: timestamps decrease inside a key, or not exact [2]
+    return rc != 1 ? rc : rung_batch(h, run, nkeys);
+}
+
 static int run_device_impl(sh_handle* h, sh_device_run* run) {
     if (!h->has_device) return fail(h, SH_E_NO_DEVICE, "no HIP device");
     if (h->app.n_streams != 1) return fail(h, SH_E_UNSUPPORTED, "sh_run_device: single-stream apps only");
@@ -1403,249 +1563,18 @@ static int run_device_impl(sh_handle* h, sh_device_run* run) {
     h->stream = (hipStream_t)run->stream;
     bool rules_seq = false;  // a rule set's aggregates left the post-pass for the general engine
     if (h->has_rules && (h->mode == 2 || !getenv("SH_DISABLE_RULES"))) {
-        const int crc = rows_for_cols(h, run);
-        if (crc) return crc;
-        int32_t* user_q = run->d_out_query;
-        uint64_t* user_seq = run->d_out_seq;
-        int rrc = run_rules(h, run);
+        const int rrc = rung_rules(h, run);
         if (rrc != 1) return rrc;
-        // the aggregates would round in parallel: the general engine adds in sequence
-        run->d_out_query = user_q;
-        run->d_out_seq = user_seq;
-        // (a set beyond the general engine's table never asks: its sequential pass ran, status 6)
-        if (h->mode == 2) return fail(h, SH_E_HIP, "rule engine: no sequential aggregate pass ran");
         rules_seq = true;
-        h->rs_last = 0;  // (the rows below are the general engine's)
     }
-    if (h->mode == 1) {
-        // general engine from fresh per-key state; the events arrive as send()
-        // calls of run->batch_events
-        if (h->T->has_absent) return fail(h, SH_E_UNSUPPORTED, "sh_run_device: absent states need sh_push_batch");
-        const int32_t nkeys = h->partitioned ? std::max(1, run->n_keys) : 1;
-        if (nf_ensure_keys(h, nkeys)) return fail(h, SH_E_OOM, "key state");
-        const nf_query& Q0 = h->T->q[0];
-        const bool aggp = h->T->n_queries == 1 && Q0.s3 && Q0.contains_agg;
-        if (aggp && !run->d_out_seq) {
-            if (h->a_seq.ensure((size_t)std::max<int64_t>(1, run->out_capacity) * 8))
-                return fail(h, SH_E_OOM, "aggregate sequence numbers");
-            run->d_out_seq = h->a_seq.as<uint64_t>();
-        }
-        {
-            // (the sequence bucket-carry engine writes typed columns / packed rows itself)
-            const int src = run_s3b(h, run, nkeys);
-            if (src != 1) {
-                if (src == SH_OK) h->kstate_stale = true;  // (no key blocks used: reset for a later user)
-                return src;
-            }
-        }
-        {
-            const int crc = rows_for_cols(h, run);
-            if (crc) return crc;
-        }
-        int rc = SH_OK;
-        int64_t rows = 0;
-        h->agg_last = rules_seq ? 2 : 0;
-        h->no_seq3 = false;
-        for (int pass = 0; pass < 2; pass++) {
-            // the rise-and-fall engine keeps no key blocks: their reset waits for a
-            // later user (kstate_stale)
-            const bool s3_run = h->T->n_queries == 1 && Q0.s3 && !h->no_seq3 && !getenv("SH_NO_SEQ3");
-            if (s3_run) {
-                h->kstate_stale = true;
-            } else {
-                hipMemsetAsync(h->n_kstate.p, 0, (size_t)nkeys * h->T->key_words * 8, h->stream);
-                h->kstate_stale = false;
-            }
-            h->started = false;
-            rc = nf_start(h);
-            if (rc) return rc;
-            nf_cols cols;
-            memset(&cols, 0, sizeof(cols));
-            for (size_t a = 0; a < h->stream_types[0].size(); a++) cols.col[0][a] = run->d_cols[a];
-            shd_batch B;
-            B.ts = run->d_ts;
-            B.stream = nullptr;
-            B.row = nullptr;
-            B.keys = h->partitioned ? run->d_keys : nullptr;
-            B.row_base = 0;
-            B.pad = 0;
-            B.seq_base = 0;
-            B.n = run->n;
-            rows = 0;
-            h->times = sh_kernel_times{};
-            h->dev_want_query = run->d_out_query != nullptr;
-            h->dev_run_ids = run->d_run;
-            rc = nf_process(h, B, nkeys, cols, run->d_out_seq, run->d_out_values, run->out_capacity, &rows, true,
-                            run->batch_events, getenv("SH_NFA_GATHER") ? nullptr : run);
-            h->dev_run_ids = nullptr;
-            run->out_count = rows;
-            if (rc == SH_OK && aggp && h->seq3_last && h->s3_agg) h->agg_last = 3;
-            if (rc != SH_OK || !aggp || !h->seq3_last || h->s3_agg) break;
-            // k_seq3 wrote the aggregators' arguments: the running values
-            int32_t arg_type[NF_MAX_OUT];
-            for (int o = 0; o < Q0.n_out; o++) arg_type[o] = Q0.s3_out_type[o];
-            const int arc = agg_post(h, run, nkeys, nullptr, 1, Q0.out_agg, arg_type, Q0.n_out);
-            if (arc < 0) return arc;
-            if (arc == 0) break;
-            h->no_seq3 = true;  // not exact: the general engine adds in sequence
-        }
-        h->no_seq3 = false;
-        if (rc == SH_OK && run->d_out_query && rows > 0) {
-            hipMemcpyAsync(run->d_out_query, h->w_oq.p, rows * 4, hipMemcpyDeviceToDevice, h->stream);
-            hipStreamSynchronize(h->stream);
-        }
-        return rc;
-    }
+    if (h->mode == 1) return run_general(h, run, rules_seq);
+    // the chain mode, from fresh per-key state
     const int32_t nkeys = h->partitioned ? std::max(1, run->n_keys) : 1;
-    // fresh per-key state
     if (ensure_keys(h, nkeys)) return fail(h, SH_E_OOM, "key state");
     hipMemsetAsync(h->d_kstate.p, 0, (size_t)nkeys * h->lay.key_bytes, h->stream);
-    shd_batch B;
-    B.ts = run->d_ts;
-    B.stream = nullptr;
-    B.row = nullptr;
-    B.keys = h->partitioned ? run->d_keys : nullptr;
-    B.row_base = 0;
-    B.seq_base = 0;
-    B.n = run->n;
-    shd_cols cols;
-    memset(&cols, 0, sizeof(cols));
-    for (size_t a = 0; a < h->stream_types[0].size(); a++) cols.col[0][a] = run->d_cols[a];
-    int64_t nm = 0;
     h->times = sh_kernel_times{};
     h->agg_last = 0;
-    // aggregators: the fast engines write raw rows with the arguments, the
-    // post-pass turns them into running values (or asks for the sequential engine)
-    const bool aggp = h->prog.agg_post != 0;
-    bool sequential = false;
-    if (aggp) {
-        if (h->prog.window_ok && h->out_mode != SHB_OUT_RAW && !h->cols_rows && !getenv("SH_BK_AGG_POST")) {
-            // packed rows / typed columns straight from the bucketed engine when its
-            // parallel carry takes the batch (the post-pass works on raw rows)
-            h->aggp_only = true;
-            const int brc = run_bucket(h, run, nkeys);
-            h->aggp_only = false;
-            if (brc == SH_OK && h->bk_agg_carried) return SH_OK;
-            if (brc != SH_OK && brc != 1) return brc;
-        }
-        const int crc = rows_for_cols(h, run);
-        if (crc) return crc;
-        if (!run->d_out_seq) {
-            if (h->a_seq.ensure((size_t)std::max<int64_t>(1, run->out_capacity) * 8))
-                return fail(h, SH_E_OOM, "aggregate sequence numbers");
-            run->d_out_seq = h->a_seq.as<uint64_t>();
-        }
-    }
-    auto finish_agg = [&](int32_t nk) {
-        const int arc = agg_post(h, run, nk, nullptr, 1, h->prog.out_agg, h->prog.out_arg_type, h->prog.n_out);
-        if (arc == 1) sequential = true;
-        return arc;
-    };
-    if (h->prog.window_ok) {
-        int brc = run_bucket(h, run, nkeys);
-        if (brc == SH_OK && aggp && !h->bk_agg_carried) {
-            const int arc = finish_agg(nkeys);
-            if (arc <= 0) return arc;
-            if (!getenv("SH_BK_AGG_POST")) {
-                // the post-pass's additions are not exact in parallel: the bucketed
-                // engine again, its carry adding in the reference's sequence
-                brc = run_bucket(h, run, nkeys, true);
-                if (brc == SH_OK && h->bk_agg_carried) return SH_OK;
-                if (brc != SH_OK && brc != 1) return brc;
-            }
-        } else if (brc != 1) {
-            return brc;
-        }
-    }
-    {
-        const int crc = rows_for_cols(h, run);
-        if (crc) return crc;
-    }
-    if (!sequential && h->prog.window_ok && h->stream_types[0].size() <= 7) {
-        const int64_t n = run->n;
-        hipStream_t st = h->stream;
-        if (ensure_ws(h, n)) return fail(h, SH_E_OOM, "workspace");
-        const int na = (int)h->stream_types[0].size();
-        const bool sorted = h->partitioned;  // unpartitioned: one segment, arrival order
-        shd_window_ws wws;
-        memset(&wws, 0, sizeof(wws));
-        if (h->v_mpos.ensure_fresh(n * 4) || h->v_flag.ensure_fresh(64) || h->v_cnts.ensure_fresh(n * 4))
-            return fail(h, SH_E_OOM, "window workspace");
-        shd_payload carry;
-        void* mid[8] = {nullptr};
-        int alias = -1;
-        if (sorted && carry_setup(h, run, &carry, mid, &alias)) return fail(h, SH_E_OOM, "window workspace");
-        wws.match_pos = h->v_mpos.as<int32_t>();
-        wws.cnt_s = h->v_cnts.as<uint32_t>();
-        wws.cnt = h->w_cnt.as<uint32_t>();
-        wws.off = h->w_off.as<uint32_t>();
-        wws.flag = h->v_flag.as<int32_t>();
-        // arrival tiles: the sorted order becomes (tile, key, arrival), so the
-        // count scatter and the ordered placement touch one tile's output window
-        // at a time (L2 / Infinity-Cache resident) instead of the whole stream
-        const int tshift = sorted ? tile_shift_for(n, nkeys) : 0;
-        hipEventRecord(h->ev[0], st);
-        shd_segment_ws ws = seg_ws(h, n);
-        const uint32_t* perm = nullptr;
-        const uint32_t* skeys = nullptr;
-        if (shd_segment_payload(&B, nkeys, &ws, st, &perm, &skeys, sorted ? &carry : nullptr, mid, tshift, 0))
-            return fail(h, SH_E_HIP, "segment launch failed");
-        shd_tiles TL;
-        memset(&TL, 0, sizeof(TL));
-        if (tshift) {
-            TL.K1 = (uint32_t)nkeys + 1;
-            TL.ntile = (uint32_t)((n + ((int64_t)1 << tshift) - 1) >> tshift);
-            TL.shift = tshift;
-            const size_t words = (size_t)TL.ntile * TL.K1;
-            if (h->v_dir.ensure_fresh(words * 8)) return fail(h, SH_E_OOM, "tile directory");
-            TL.dstart = h->v_dir.as<uint32_t>();
-            TL.dend = h->v_dir.as<uint32_t>() + words;
-            if (shd_tile_dir(skeys, n, tshift, TL.K1, TL.ntile, (uint32_t*)TL.dstart, (uint32_t*)TL.dend, st))
-                return fail(h, SH_E_HIP, "tile directory launch failed");
-        }
-        hipEventRecord(h->ev[1], st);
-        const int64_t* sts = sorted ? h->v_sts.as<int64_t>() : run->d_ts;
-        const void* scols[32];
-        for (int a = 0; a < na; a++) scols[a] = sorted ? (const void*)h->v_scol[a].p : run->d_cols[a];
-        if (alias >= 0) scols[alias] = skeys;  // the partition column in key-segment order is the sorted key
-        if (h->jit_state == 0) {
-            if (getenv("SH_DISABLE_JIT")) {
-                h->jit_state = -1;
-                h->jit_err = "disabled by SH_DISABLE_JIT";
-            } else {
-                h->jit_state = shj_window_load(&h->prog, &h->jit, &h->jit_err) == 0 ? 1 : -1;
-            }
-        }
-        int wrc = shd_window(h->d_prog.as<shp_program>(), &h->prog, &B, nkeys, perm, skeys, sts, scols, &wws,
-                             h->d_cols_desc.as<shd_cols>(), h->w_scan.as<uint32_t>(), run->d_out_seq, nullptr,
-                             run->d_out_values, nullptr, run->out_capacity, &nm, st, h->ev[2],
-                             h->jit_state == 1 ? &h->jit : nullptr, tshift ? &TL : nullptr);
-        hipEventRecord(h->ev[3], st);
-        if (hipStreamSynchronize(st) != hipSuccess) return fail(h, SH_E_HIP, "device error in window engine");
-        if (wrc < 0) return fail(h, SH_E_HIP, "window engine launch failed");
-        run->out_count = nm;
-        if (wrc == 2) return fail(h, SH_E_MORE, "output capacity too small");
-        if (wrc == 0 && run->d_out_query && nm > 0) hipMemsetAsync(run->d_out_query, 0, nm * 4, st);
-        if (wrc == 0) {
-            hipEventElapsedTime(&h->times.segment_ms, h->ev[0], h->ev[1]);
-            hipEventElapsedTime(&h->times.advance_ms, h->ev[1], h->ev[2]);
-            hipEventElapsedTime(&h->times.emit_ms, h->ev[2], h->ev[3]);
-            hipEventElapsedTime(&h->times.total_ms, h->ev[0], h->ev[3]);
-            h->times.advance_launches = 1;
-            if (!aggp) return SH_OK;
-            const int arc = finish_agg(nkeys);
-            if (arc <= 0) return arc;
-        }
-        // wrc == 1: timestamps decrease inside a key -> sequential per-key engine
-    }
-    int rc = run_batch(h, B, nkeys, cols, run->d_out_seq, nullptr, run->d_out_values, nullptr, run->out_capacity,
-                       &nm, true);
-    run->out_count = nm;
-    if (rc == SH_OK && run->d_out_query && nm > 0) {
-        hipMemsetAsync(run->d_out_query, 0, nm * 4, h->stream);
-        hipStreamSynchronize(h->stream);
-    }
-    return rc;
+    return run_chain(h, run, nkeys);
 }
 
 static int run_device_cols(sh_handle* h, sh_device_run* run);

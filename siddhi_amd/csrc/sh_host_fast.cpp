@@ -351,10 +351,7 @@ static int rules_finish(sh_handle* h, sh_device_run* run, int64_t m, int32_t nke
     hipStream_t st = h->stream;
     hipEventRecord(h->ev[3], st);
     if (hipStreamSynchronize(st) != hipSuccess) return fail(h, SH_E_HIP, "device error in the rule engine");
-    hipEventElapsedTime(&h->times.segment_ms, h->ev[0], h->ev[1]);
-    hipEventElapsedTime(&h->times.advance_ms, h->ev[1], h->ev[2]);
-    hipEventElapsedTime(&h->times.emit_ms, h->ev[2], h->ev[3]);
-    hipEventElapsedTime(&h->times.total_ms, h->ev[0], h->ev[3]);
+    phase_times(h);
     h->times.advance_launches = 1;
     if (h->r_aggp && m > 0) {
         const int arc = agg_post(h, run, nkeys, run->d_out_query, (int)h->r_rules.size(), h->r_agg, h->r_argt,
@@ -895,10 +892,7 @@ int rules_step(sh_handle* h) {
         h->o_nulls.resize(base * h->n_out);
         return rules_step_fail(h, SH_E_HIP, "device error in the rule step");
     }
-    hipEventElapsedTime(&h->times.segment_ms, h->ev[0], h->ev[1]);
-    hipEventElapsedTime(&h->times.advance_ms, h->ev[1], h->ev[2]);
-    hipEventElapsedTime(&h->times.emit_ms, h->ev[2], h->ev[3]);
-    hipEventElapsedTime(&h->times.total_ms, h->ev[0], h->ev[3]);
+    phase_times(h);
     h->rc_cur = 1 - h->rc_cur;
     h->rc_rows = nrows;
     h->rc_pairs = npairs;
@@ -917,246 +911,120 @@ int rules_step(sh_handle* h) {
     return SH_OK;
 }
 
+shd_batch device_batch(const sh_handle* h, const sh_device_run* run) {
+    return shd_batch{run->d_ts, nullptr, nullptr, h->partitioned ? run->d_keys : nullptr, 0, 0, 0, run->n};
+}
+
+// the four phase times of sh_kernel_times from the events ev[0..3]
+void phase_times(sh_handle* h) {
+    hipEventElapsedTime(&h->times.segment_ms, h->ev[0], h->ev[1]);
+    hipEventElapsedTime(&h->times.advance_ms, h->ev[1], h->ev[2]);
+    hipEventElapsedTime(&h->times.emit_ms, h->ev[2], h->ev[3]);
+    hipEventElapsedTime(&h->times.total_ms, h->ev[0], h->ev[3]);
+}
+
+// ---- the scaffold of the two bucket-partition engines (run_bucket, run_s3b)
+
+// the plan's shape, and the workspaces and pointers both engines fill; matcher: the
+// window matcher's plan (event-sized scan workspace, packed timestamps, the segment
+// table), else the sequence carry's. Called after the engine's last "not applicable"
+// answer; the staged, match-stream and aggregate columns are the caller's
+static int bk_workspace(sh_handle* h, const sh_device_run* run, int kb, bool matcher, const char* oom, shb_plan* B) {
+    const int64_t n = run->n;
+    B->n = n;
+    B->nt = (int32_t)((n + SHB_TILE - 1) / SHB_TILE);
+    B->et1 = B->nt;
+    B->kb = kb;
+    B->no_ts = matcher ? 0 : 1;
+    B->tstride = (B->nt + 63) & ~63;
+    const int64_t nt = B->nt, slots = nt * SHB_TILE;  // slots: the tiles' bucket order
+    if (ensure_ws(h, matcher ? std::max(n, nt + 1) : nt + 1) || h->bk_w0.ensure_fresh(slots * 4) ||
+        h->bk_sp.ensure_fresh(n * 2) || h->bk_toff.ensure_fresh(nt * SHB_TOFF * 2) || h->bk_cnt.ensure_fresh(slots) ||
+        h->bk_mstart.ensure_fresh(nt * SHB_NB * 4) || h->bk_tpre.ensure_fresh(nt * 8) ||
+        h->bk_tfirst.ensure_fresh(nt * 8) || h->bk_hstart.ensure_fresh(nt * 4) ||
+        h->bk_ttot.ensure_fresh((nt + 1) * 4) || h->bk_flag.ensure_fresh(64) || h->bk_rd.ensure(64) ||
+        h->bk_tofft.ensure_fresh((int64_t)(SHB_NB + 1) * B->tstride * 2) ||
+        // the matcher's segment table: each bucket's segment lengths summed over the tiles,
+        // written once per step by the partition (12.5 MB at 100M events)
+        (matcher && (h->bk_tpfx.ensure_fresh((int64_t)SHB_NB * B->tstride * 4) ||
+                     h->bk_tpfb.ensure_fresh((int64_t)SHB_NB * (B->tstride / 64 + 1) * 4))))
+        return fail(h, SH_E_OOM, oom);
+    B->ts = run->d_ts;
+    B->keys = run->d_keys;
+    B->w0 = h->bk_w0.as<uint32_t>();
+    B->sp = h->bk_sp.as<uint16_t>();
+    B->toff = h->bk_toff.as<uint16_t>();
+    B->tofft = h->bk_tofft.as<uint16_t>();
+    B->tpfx = matcher ? h->bk_tpfx.as<uint32_t>() : nullptr;
+    B->tpfb = matcher ? h->bk_tpfb.as<uint32_t>() : nullptr;
+    B->cnt = h->bk_cnt.as<uint8_t>();
+    B->mstart = h->bk_mstart.as<uint32_t>();
+    B->tpre = h->bk_tpre.as<int64_t>();
+    B->tfirst = h->bk_tfirst.as<int64_t>();
+    B->hstart = h->bk_hstart.as<int32_t>();
+    B->ttot = h->bk_ttot.as<uint32_t>();
+    B->flag = h->bk_flag.as<int32_t>();
+    B->ms_ctr = h->bk_flag.as<uint32_t>() + 4;
+    static const bool prof = getenv("SH_BK_PROFILE") != nullptr;
+    if (prof) {
+        if (h->bk_prof.ensure_fresh(128)) return fail(h, SH_E_OOM, "profile");
+        hipMemsetAsync(h->bk_prof.p, 0, 128, h->stream);
+        B->prof = h->bk_prof.as<unsigned long long>();
+    }
+    return SH_OK;
+}
+
+// ev[0], the flag and total words cleared, the tile-local bucket partition, ev[1]
+static int bk_begin(sh_handle* h, const sh_device_run* run, int32_t nkeys, shb_plan* B, const char* what) {
+    hipStream_t st = h->stream;
+    hipEventRecord(h->ev[0], st);
+    hipMemsetAsync(B->flag, 0, 32, st);  // flag word + match-stream allocator
+    hipMemsetAsync(B->ttot, 0, ((int64_t)B->nt + 1) * 4, st);
+    if (shb_partition(run->d_keys, run->d_ts, nkeys, B, st)) return fail(h, SH_E_HIP, what);
+    hipEventRecord(h->ev[1], st);
+    return SH_OK;
+}
+
+// ev[3] and the read-back of the device's flag word and match total
+static int bk_end(sh_handle* h, const shb_plan* B, const char* what, int32_t* flag, int64_t* total) {
+    hipStream_t st = h->stream;
+    hipEventRecord(h->ev[3], st);
+    hipMemcpyAsync(h->bk_rd.as<void>(0), B->flag, 4, hipMemcpyDeviceToHost, st);
+    hipMemcpyAsync(h->bk_rd.as<void>(8), B->ttot + B->nt, 4, hipMemcpyDeviceToHost, st);
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(h, SH_E_HIP, what);
+    *flag = *h->bk_rd.as<int32_t>(0);
+    *total = *h->bk_rd.as<uint32_t>(8);
+    return SH_OK;
+}
+
+// the engines' common answer once the caller has judged its own flag bits: a bad key
+// id, 1 for any other premise that failed on the device, the match count against the
+// capacity, the phase times; *last = 1 (bk_last / s3b_last) when the rows stand
+static int bk_close(sh_handle* h, sh_device_run* run, int32_t flag, int64_t total, int* last, const char* what) {
+    hipStream_t st = h->stream;
+    if (flag & SHB_F_KEY) return fail(h, SH_E_INVALID_ARG, "partition key id >= n_keys");
+    if (flag) return 1;
+    run->out_count = total;
+    if (total > run->out_capacity) return fail(h, SH_E_MORE, "output capacity too small");
+    if (run->d_out_query && total > 0) hipMemsetAsync(run->d_out_query, 0, total * 4, st);
+    phase_times(h);
+    h->times.advance_launches = 1;
+    *last = 1;
+    return hipStreamSynchronize(st) == hipSuccess ? SH_OK : fail(h, SH_E_HIP, what);
+}
+
 // chunks per time segment of run_bucket's matcher / emitter pipeline (C2: 8 chunks 3.90 ms
 // per step, 16 3.70, 32 3.66-3.68 against the single launch's 3.70-3.74,
 // profiles/c2_pipeline_ab.txt)
 static constexpr int SH_BK_SEG_CHUNKS = 32;
 
-// bucketed window engine (sh_bucket.hip): partitioned window programs with a
-// consumer-side form and a null-free projection; 0 ok, 1 = not applicable or a
-// premise failed on the device (the caller runs the general window path),
-// SH_E_MORE = output capacity too small (out_count = matches), <0 error
-int run_bucket(sh_handle* h, sh_device_run* run, int32_t nkeys, bool force_carry) {
-    static const bool off = getenv("SH_DISABLE_BUCKET") != nullptr;
-    h->bk_last = 0;
-    const shp_program& P = h->prog;
-    const int64_t n = run->n;
-    if (off || !h->partitioned || nkeys < 1024 || !P.out_fast || n < SHB_TILE) return 1;
-    // a max / min select is not offered to this engine yet: the window engine writes
-    // its arguments and the post-pass (sh_agg.hip "max / min") forms the values
-    for (int o = 0; o < P.n_out; o++)
-        if (P.out_agg[o] == SH_AGG_MAX || P.out_agg[o] == SH_AGG_MIN) return 1;
-    const int kb = std::max(0, bits_for((uint64_t)(nkeys - 1)) - 8);
-    if (kb > 8) return 1;
-    // select list: e2-side values (and e1's partition attribute, equal to e2's
-    // for these types) from the consumer row; other e1-side values ride the match stream
-    shb_out O;
-    memset(&O, 0, sizeof(O));
-    O.n_out = P.n_out;
-    int ms[SHB_MAX_MS], n_ms = 0;
-    const int part_attr = h->part_attr0;
-    for (int o = 0; o < P.n_out; o++) {
-        const int a = P.out_attr[o], t = P.attr_type[0][a];
-        O.type[o] = t;
-        const bool fold = a == part_attr && (t == SH_T_STRING || t == SH_T_INT || t == SH_T_LONG || t == SH_T_BOOL);
-        if (P.out_slot[o] == 1 || fold) {
-            O.kind[o] = 1;
-            O.src[o] = run->d_cols[a];
-            continue;
-        }
-        int m = 0;
-        while (m < n_ms && ms[m] != a) m++;
-        if (m == n_ms) {
-            if (n_ms == SHB_MAX_MS) return 1;
-            ms[n_ms++] = a;
-        }
-        O.kind[o] = 0;
-        O.src[o] = (const void*)(intptr_t)m;  // resolved below
-    }
-    if (h->bk_state == 0) {
-        const int lrc = shj_bucket_load(&P, ms, n_ms, &h->bk, &h->bk_err);
-        h->bk_state = lrc == 0 ? 1 : (lrc == -1 ? -2 : -1);  // -2: no consumer-side form (not applicable)
-    }
-    if (h->bk_state != 1) return 1;
+// run_bucket's launches between the partition (ev[1]) and the read-back: the matcher,
+// the carry of the aggregates (AG, or nullptr), the scans and the emitter; ev[2] is
+// recorded between the matchers and the emitters' tail
+static int bucket_launch(sh_handle* h, sh_device_run* run, shb_plan& B, const shb_out& O, const shb_cols& OC,
+                         const shb_aggc* AG) {
     hipStream_t st = h->stream;
-    shb_plan B;
-    memset(&B, 0, sizeof(B));
-    if (n >= ((int64_t)1 << 32) - SHB_TILE) return 1;  // event indices are 32-bit on this engine
-    B.n = n;
-    B.nt = (int32_t)((n + SHB_TILE - 1) / SHB_TILE);
-    B.kb = kb;
-    // tiles per matcher chunk: 15/16 of the pass's consumer limit in events of a
-    // bucket at uniform keys (32 per tile; 60 tiles at 2,048), so a chunk and its
-    // halo fit the LDS span; denser buckets split (C2: 60 tiles 1.90 ms, 56 1.97-1.99,
-    // 52 2.07, 64 2.50 in one call, profiles/r6_c2_ct_ab.txt)
-    static const int ct_env = getenv("SH_BK_CT") ? atoi(getenv("SH_BK_CT")) : 0;
-    B.ct = ct_env > 0 ? std::min(ct_env, SHB_CT_MAX) : std::min(shj_bucket_chunk() * 15 / 512, SHB_CT_MAX);
-    B.n_chunks = (B.nt + B.ct - 1) / B.ct;
-    const int64_t slots = (int64_t)B.nt * SHB_TILE;  // the tiles' bucket order
-    if (ensure_ws(h, std::max<int64_t>(n, (int64_t)B.nt + 1)) || h->bk_w0.ensure_fresh(slots * 4) ||
-        h->bk_sp.ensure_fresh(n * 2) || h->bk_toff.ensure_fresh((int64_t)B.nt * SHB_TOFF * 2) ||
-        h->bk_cnt.ensure_fresh(slots) || h->bk_mstart.ensure_fresh((int64_t)B.nt * SHB_NB * 4) ||
-        h->bk_tpre.ensure_fresh((int64_t)B.nt * 8) || h->bk_tfirst.ensure_fresh((int64_t)B.nt * 8) ||
-        h->bk_hstart.ensure_fresh((int64_t)B.nt * 4) || h->bk_ttot.ensure_fresh(((int64_t)B.nt + 1) * 4) ||
-        h->bk_flag.ensure_fresh(64) || h->bk_rd.ensure(64))
-        return fail(h, SH_E_OOM, "bucket workspace");
-    B.n_staged = h->bk.n_staged;
-    for (int k = 0; k < B.n_staged; k++) {
-        const int a = h->bk.staged_attr[k];
-        const int w = type_width(P.attr_type[0][a]);
-        if (h->bk_st[k].ensure_fresh(slots * w)) return fail(h, SH_E_OOM, "bucket workspace");
-        B.st_src[k] = run->d_cols[a];
-        B.st_dst[k] = h->bk_st[k].p;
-        B.st_width[k] = w;
-    }
-    // match stream: one region of SHB_SPAN values per matcher workgroup (its first
-    // pass), then a shared tail for further passes; every partial is consumed at
-    // most once, so n values suffice for the tail
-    B.n_ms = n_ms;
-    const int64_t ms_vals = (int64_t)SHB_NB * B.n_chunks * SHB_SPAN + n;
-    for (int m = 0; m < n_ms; m++) {
-        const int w = type_width(P.attr_type[0][ms[m]]);
-        if (h->bk_ms[m].ensure_fresh(ms_vals * w)) return fail(h, SH_E_OOM, "match stream");
-        B.ms[m] = h->bk_ms[m].p;
-        B.ms_width[m] = w;
-    }
-    int ms_of[SHB_MAX_OUT];
-    for (int o = 0; o < O.n_out; o++) {
-        ms_of[o] = O.kind[o] == 0 ? (int)(intptr_t)O.src[o] : -1;
-        if (O.kind[o] == 0) O.src[o] = B.ms[ms_of[o]];
-    }
-    // aggregators carried per key in arrival order (k_bk_aggc: the reference's own
-    // additions, no exactness proof): e1-side arguments from one 4-byte match-stream
-    // column, e2-side ones from up to two staged columns (one of them 4-byte), count()
-    // without one; anything else takes the post-pass (sh_agg.hip)
-    shb_aggc AG;
-    memset(&AG, 0, sizeof(AG));
-    AG.e1_col = AG.e2_col[0] = AG.e2_col[1] = -1;
-    // k_bk_aggp first (the additions as a segmented prefix, exact in 64-bit fixed point,
-    // refused on the device by a value that is not); k_bk_aggc (every key of a bucket
-    // walked in one workgroup: C2's 40 keys per bucket leave most lanes idle -- 28 ms
-    // against the post-pass's 8.7) when the post-pass refuses too, or SH_BK_AGGC=1
-    const bool aggc_env = getenv("SH_BK_AGGC") != nullptr;
-    const bool aggp_off = getenv("SH_BK_AGGP") && getenv("SH_BK_AGGP")[0] == '0';
-    const bool par = !force_carry && !aggc_env && !aggp_off && !h->aggp_refused && run->n < ((int64_t)1 << 31);
-    bool carry = P.agg_post && !getenv("SH_BK_AGG_POST") && (force_carry || aggc_env || par);
-    AG.parallel = par ? 1 : 0;
-    // (the running values go by match-stream position; by output row, through a per-slot
-    // row map, measured 8.39 vs 7.65 ms/step in round 5: removed)
-    int agg_of[SHB_MAX_OUT];
-    for (int o = 0; o < P.n_out; o++) agg_of[o] = -1;
-    for (int o = 0; o < P.n_out && carry; o++) {
-        const int ak = P.out_agg[o];
-        if (ak == SH_AGG_NONE) continue;
-        if (AG.n == SHB_MAX_AGG || (ak != SH_AGG_SUM && ak != SH_AGG_AVG && ak != SH_AGG_COUNT)) {
-            carry = false;
-            break;
-        }
-        const int i = AG.n++;
-        AG.kind[i] = ak;
-        agg_of[o] = i;
-        if (ak == SH_AGG_COUNT) {
-            AG.side[i] = 3;
-            continue;
-        }
-        const int a = P.out_attr[o], t = P.attr_type[0][a];
-        if (t != SH_T_INT && t != SH_T_FLOAT && t != SH_T_LONG && t != SH_T_DOUBLE) {
-            carry = false;
-            break;
-        }
-        const int w = type_width(t);
-        if (P.out_slot[o] == 0 && ms_of[o] >= 0 && w == 4 && (AG.e1_col < 0 || AG.e1_col == ms_of[o])) {
-            AG.e1_col = ms_of[o];
-            AG.e1_type = t;
-            AG.side[i] = 0;
-        } else if (P.out_slot[o] == 1) {
-            // the consumer's column at its slot: staged by the partition (the matcher's
-            // own staged columns first, then the carry's)
-            int k = 0;
-            while (k < B.n_staged && (B.st_src[k] != run->d_cols[a])) k++;
-            if (k == B.n_staged) {
-                if (B.n_staged == SHB_MAX_STAGED || h->bk_st[k].ensure_fresh(slots * w))
-                    return B.n_staged == SHB_MAX_STAGED ? 1 : fail(h, SH_E_OOM, "bucket workspace");
-                B.st_src[k] = run->d_cols[a];
-                B.st_dst[k] = h->bk_st[k].p;
-                B.st_width[k] = w;
-                B.n_staged++;
-            }
-            int c = (AG.e2_col[0] == k) ? 0 : (AG.e2_col[1] == k ? 1 : -1);
-            if (c < 0) {
-                if (AG.e2_col[0] < 0) c = 0;
-                else if (AG.e2_col[1] < 0 && w == 4) c = 1;
-                else if (AG.e2_col[1] < 0 && type_width(AG.e2_type[0]) == 4) {
-                    // keep the 8-byte column in slot 0
-                    AG.e2_col[1] = AG.e2_col[0];
-                    AG.e2_type[1] = AG.e2_type[0];
-                    for (int j = 0; j < i; j++)
-                        if (AG.side[j] == 1) AG.side[j] = 2;
-                    c = 0;
-                } else {
-                    carry = false;
-                    break;
-                }
-                AG.e2_col[c] = k;
-                AG.e2_type[c] = t;
-            }
-            AG.side[i] = 1 + c;
-        } else {
-            carry = false;
-        }
-    }
-    if (carry) {
-        for (int i = 0; i < AG.n; i++) {
-            if (h->bk_agg[i].ensure_fresh(ms_vals * 8)) return fail(h, SH_E_OOM, "aggregate columns");
-            AG.out[i] = h->bk_agg[i].p;
-        }
-        for (int o = 0; o < O.n_out; o++)
-            if (agg_of[o] >= 0) {
-                O.kind[o] = 0;
-                O.src[o] = AG.out[agg_of[o]];
-                O.type[o] = P.out_type[o];
-            }
-    }
-    if (h->aggp_only && !(carry && AG.parallel)) return 1;
-    h->bk_agg_carried = false;
-    shb_cols OC;
-    memset(&OC, 0, sizeof(OC));
-    if (!P.agg_post || carry) {
-        int32_t wd[SHB_MAX_OUT];
-        for (int o = 0; o < O.n_out; o++) wd[o] = type_width(O.type[o]);
-        direct_layout(h, run, wd, O.n_out, &OC);
-    }
-    B.ts = run->d_ts;
-    B.keys = run->d_keys;
-    B.w0 = h->bk_w0.as<uint32_t>();
-    B.sp = h->bk_sp.as<uint16_t>();
-    B.toff = h->bk_toff.as<uint16_t>();
-    B.tstride = (B.nt + 63) & ~63;
-    if (h->bk_tofft.ensure_fresh((int64_t)(SHB_NB + 1) * B.tstride * 2)) return fail(h, SH_E_OOM, "bucket workspace");
-    B.tofft = h->bk_tofft.as<uint16_t>();
-    // the matcher's segment table: each bucket's segment lengths summed over the tiles,
-    // written once per step by the partition (12.5 MB at 100M events)
-    if (h->bk_tpfx.ensure_fresh((int64_t)SHB_NB * B.tstride * 4) ||
-        h->bk_tpfb.ensure_fresh((int64_t)SHB_NB * (B.tstride / 64 + 1) * 4))
-        return fail(h, SH_E_OOM, "bucket workspace");
-    B.tpfx = h->bk_tpfx.as<uint32_t>();
-    B.tpfb = h->bk_tpfb.as<uint32_t>();
-    B.cnt = h->bk_cnt.as<uint8_t>();
-    B.mstart = h->bk_mstart.as<uint32_t>();
-    B.tpre = h->bk_tpre.as<int64_t>();
-    B.tfirst = h->bk_tfirst.as<int64_t>();
-    B.hstart = h->bk_hstart.as<int32_t>();
-    B.within = std::max<int64_t>(0, P.within_ms);
-    B.ttot = h->bk_ttot.as<uint32_t>();
-    B.flag = h->bk_flag.as<int32_t>();
-    B.ms_ctr = h->bk_flag.as<uint32_t>() + 4;
-    static const bool prof = getenv("SH_BK_PROFILE") != nullptr;
-    if (prof) {
-        if (h->bk_prof.ensure_fresh(128)) return fail(h, SH_E_OOM, "profile");
-        hipMemsetAsync(h->bk_prof.p, 0, 128, h->stream);
-        B.prof = h->bk_prof.as<unsigned long long>();
-    }
-    // packed timestamps: ts - tbase in 32 - kb bits, centred on the first event
-    hipMemcpyAsync(h->bk_rd.p, run->d_ts, 8, hipMemcpyDeviceToHost, st);
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(h, SH_E_HIP, "bucket: timestamp read");
-    B.tbase = *h->bk_rd.as<int64_t>() - ((int64_t)1 << (31 - kb));
-    hipEventRecord(h->ev[0], st);
-    hipMemsetAsync(B.flag, 0, 32, st);  // flag word + match-stream allocator
-    hipMemsetAsync(B.ttot, 0, ((int64_t)B.nt + 1) * 4, st);
-    if (shb_partition(run->d_keys, run->d_ts, nkeys, &B, st)) return fail(h, SH_E_HIP, "bucket partition launch failed");
-    hipEventRecord(h->ev[1], st);
     void* args[] = {&B};
-    B.et1 = B.nt;
     // The matcher (VALU and LDS bound) and the emitter (parked on memory) overlap over
     // time segments of whole chunks: the matchers of segment 0, 1, ... on the caller's
     // stream, an event after each; behind that event, on the handle's side stream, the
@@ -1170,7 +1038,7 @@ int run_bucket(sh_handle* h, sh_device_run* run, int32_t nkeys, bool force_carry
     if (const char* e = getenv("SH_BK_SEG")) seg = atoi(e);
     if (seg > 0) seg = std::max(seg, (B.n_chunks + sh_handle::SH_BK_SEGS - 1) / sh_handle::SH_BK_SEGS);
     const int n_seg = seg > 0 ? (B.n_chunks + seg - 1) / seg : 1;
-    const bool piped = !carry && !prof && (n_seg >= 2 || (seg > 0 && getenv("SH_BK_SEG")));
+    const bool piped = !AG && !B.prof && (n_seg >= 2 || (seg > 0 && getenv("SH_BK_SEG")));
     if (piped && !h->bk_side) {
         // (created with the highest priority it lost: 3.706 against 3.682 ms per step)
         if (hipStreamCreateWithFlags(&h->bk_side, hipStreamNonBlocking) != hipSuccess) {
@@ -1216,18 +1084,120 @@ int run_bucket(sh_handle* h, sh_device_run* run, int32_t nkeys, bool force_carry
         if (hipModuleLaunchKernel((hipFunction_t)h->bk.match, (unsigned)(SHB_NB * B.n_chunks), 1, 1, 512, 1, 1, 0, st,
                                   args, nullptr) != hipSuccess)
             return fail(h, SH_E_HIP, "shb_match launch failed");
-        if (carry && shb_agg_carry(&B, &AG, st)) return fail(h, SH_E_HIP, "aggregate carry launch failed");
+        if (AG && shb_agg_carry(&B, AG, st)) return fail(h, SH_E_HIP, "aggregate carry launch failed");
         if (shb_finish(&B, h->w_scan.as<uint32_t>(), st)) return fail(h, SH_E_HIP, "bucket scan launch failed");
         hipEventRecord(h->ev[2], st);
         if (shb_emit(&B, &O, &OC, 0, run->d_out_seq, run->d_out_values, run->out_capacity, st))
             return fail(h, SH_E_HIP, "bucket emit launch failed");
     }
-    hipEventRecord(h->ev[3], st);
-    hipMemcpyAsync(h->bk_rd.as<void>(0), B.flag, 4, hipMemcpyDeviceToHost, st);
-    hipMemcpyAsync(h->bk_rd.as<void>(8), B.ttot + B.nt, 4, hipMemcpyDeviceToHost, st);
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(h, SH_E_HIP, "device error in bucket engine");
-    const int32_t flag = *h->bk_rd.as<int32_t>(0);
-    const int64_t total = *h->bk_rd.as<uint32_t>(8);
+    return SH_OK;
+}
+
+// bucketed window engine (sh_bucket.hip): partitioned window programs with a
+// consumer-side form and a null-free projection; 0 ok, 1 = not applicable or a
+// premise failed on the device (the caller runs the general window path),
+// SH_E_MORE = output capacity too small (out_count = matches), <0 error.
+// mode: how an aggregating select's running values are formed; a select the carry
+// plan does not take leaves the arguments in the rows whatever the mode (res->carried
+// says which), and the device's refusal of the parallel carry answers 1 with
+// res->refused: the caller runs the next mode
+int run_bucket(sh_handle* h, sh_device_run* run, int32_t nkeys, BkAgg mode, BkRun* res) {
+    static const bool off = getenv("SH_DISABLE_BUCKET") != nullptr;
+    h->bk_last = 0;
+    *res = BkRun{};
+    const shp_program& P = h->prog;
+    const int64_t n = run->n;
+    if (off || !h->partitioned || nkeys < 1024 || !P.out_fast || n < SHB_TILE) return 1;
+    // a max / min select is not offered to this engine yet: the window engine writes
+    // its arguments and the post-pass (sh_agg.hip "max / min") forms the values
+    for (int o = 0; o < P.n_out; o++)
+        if (P.out_agg[o] == SH_AGG_MAX || P.out_agg[o] == SH_AGG_MIN) return 1;
+    const int kb = std::max(0, bits_for((uint64_t)(nkeys - 1)) - 8);
+    if (kb > 8) return 1;
+    shb_out O;
+    shb_select S;
+    if (shb_plan_select(P, h->part_attr0, run->d_cols, &O, &S)) return 1;
+    if (h->bk_state == 0) {
+        const int lrc = shj_bucket_load(&P, S.ms, S.n_ms, &h->bk, &h->bk_err);
+        h->bk_state = lrc == 0 ? 1 : (lrc == -1 ? -2 : -1);  // -2: no consumer-side form (not applicable)
+    }
+    if (h->bk_state != 1) return 1;
+    if (n >= ((int64_t)1 << 32) - SHB_TILE) return 1;  // event indices are 32-bit on this engine
+    shb_plan B{};
+    B.n_staged = h->bk.n_staged;
+    for (int k = 0; k < B.n_staged; k++) {
+        B.st_src[k] = run->d_cols[h->bk.staged_attr[k]];
+        B.st_width[k] = type_width(P.attr_type[0][h->bk.staged_attr[k]]);
+    }
+    // k_bk_aggp (the additions as a segmented prefix, exact in 64-bit fixed point, refused
+    // on the device by a value that is not) or k_bk_aggc (the reference's own additions,
+    // no exactness proof; every key of a bucket walked in one workgroup: C2's 40 keys per
+    // bucket leave most lanes idle -- 28 ms against the post-pass's 8.7)
+    // (the running values go by match-stream position; by output row, through a per-slot
+    // row map, measured 8.39 vs 7.65 ms/step in round 5: removed)
+    shb_aggc AG{};
+    int agg_of[SHB_MAX_OUT];
+    bool carry = P.agg_post && mode != BK_AGG_ROWS;
+    if (carry) {
+        const shb_carry_plan cp = shb_plan_carry(P, run->d_cols, S.ms_of, &B, &AG, agg_of);
+        if (cp == SHB_CARRY_NA) return 1;
+        carry = cp == SHB_CARRY;
+    }
+    AG.parallel = mode == BK_AGG_PAR ? 1 : 0;
+    // (the post-pass reads raw rows: never written into the caller's packed rows or typed columns)
+    if (P.agg_post && !carry && h->out_mode != SHB_OUT_RAW && !h->cols_rows) return 1;
+    // every pointer below is taken after its buffer's last ensure_fresh
+    if (const int wrc = bk_workspace(h, run, kb, true, "bucket workspace", &B)) return wrc;
+    // tiles per matcher chunk: 15/16 of the pass's consumer limit in events of a
+    // bucket at uniform keys (32 per tile; 60 tiles at 2,048), so a chunk and its
+    // halo fit the LDS span; denser buckets split (C2: 60 tiles 1.90 ms, 56 1.97-1.99,
+    // 52 2.07, 64 2.50 in one call, profiles/r6_c2_ct_ab.txt)
+    static const int ct_env = getenv("SH_BK_CT") ? atoi(getenv("SH_BK_CT")) : 0;
+    B.ct = ct_env > 0 ? std::min(ct_env, SHB_CT_MAX) : std::min(shj_bucket_chunk() * 15 / 512, SHB_CT_MAX);
+    B.n_chunks = (B.nt + B.ct - 1) / B.ct;
+    B.within = std::max<int64_t>(0, P.within_ms);
+    for (int k = 0; k < B.n_staged; k++) {
+        if (h->bk_st[k].ensure_fresh((int64_t)B.nt * SHB_TILE * B.st_width[k])) return fail(h, SH_E_OOM, "bucket workspace");
+        B.st_dst[k] = h->bk_st[k].p;
+    }
+    // match stream: one region of SHB_SPAN values per matcher workgroup (its first
+    // pass), then a shared tail for further passes; every partial is consumed at
+    // most once, so n values suffice for the tail
+    B.n_ms = S.n_ms;
+    const int64_t ms_vals = (int64_t)SHB_NB * B.n_chunks * SHB_SPAN + n;
+    for (int m = 0; m < S.n_ms; m++) {
+        B.ms_width[m] = type_width(P.attr_type[0][S.ms[m]]);
+        if (h->bk_ms[m].ensure_fresh(ms_vals * B.ms_width[m])) return fail(h, SH_E_OOM, "match stream");
+        B.ms[m] = h->bk_ms[m].p;
+    }
+    for (int i = 0; carry && i < AG.n; i++) {
+        if (h->bk_agg[i].ensure_fresh(ms_vals * 8)) return fail(h, SH_E_OOM, "aggregate columns");
+        AG.out[i] = h->bk_agg[i].p;
+    }
+    for (int o = 0; o < O.n_out; o++) {
+        if (S.ms_of[o] >= 0) O.src[o] = B.ms[S.ms_of[o]];
+        if (carry && agg_of[o] >= 0) {
+            O.kind[o] = 0;
+            O.src[o] = AG.out[agg_of[o]];
+            O.type[o] = P.out_type[o];
+        }
+    }
+    shb_cols OC{};
+    if (!P.agg_post || carry) {
+        int32_t wd[SHB_MAX_OUT];
+        for (int o = 0; o < O.n_out; o++) wd[o] = type_width(O.type[o]);
+        direct_layout(h, run, wd, O.n_out, &OC);
+    }
+    // packed timestamps: ts - tbase in 32 - kb bits, centred on the first event
+    hipStream_t st = h->stream;
+    hipMemcpyAsync(h->bk_rd.p, run->d_ts, 8, hipMemcpyDeviceToHost, st);
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(h, SH_E_HIP, "bucket: timestamp read");
+    B.tbase = *h->bk_rd.as<int64_t>() - ((int64_t)1 << (31 - kb));
+    if (const int brc = bk_begin(h, run, nkeys, &B, "bucket partition launch failed")) return brc;
+    if (const int lrc = bucket_launch(h, run, B, O, OC, carry ? &AG : nullptr)) return lrc;
+    int32_t flag = 0;
+    int64_t total = 0;
+    if (const int erc = bk_end(h, &B, "device error in bucket engine", &flag, &total)) return erc;
     if (B.prof) {
         unsigned long long pr[16];
         hipMemcpy(pr, B.prof, 128, hipMemcpyDeviceToHost);
@@ -1243,30 +1213,21 @@ int run_bucket(sh_handle* h, sh_device_run* run, int32_t nkeys, bool force_carry
                             "sort %llu walk %llu\n",
                     pr[8], pr[9], pr[10], pr[11], pr[12]);
     }
-    if (flag & SHB_F_KEY) return fail(h, SH_E_INVALID_ARG, "partition key id >= n_keys");
     if (flag == SHB_F_AGG && carry && AG.parallel) {
-        // a value the fixed point cannot hold exactly (or a chunk too dense): the
-        // batch again without the carry, the post-pass (or k_bk_aggc) adding instead
-        // The refusal sticks to the handle: data that fails the fixed-point test once
-        // (a price such as 12.34) fails it in every batch, and each refused attempt costs
-        // a whole bucketed pipeline
-        h->aggp_refused = true;
-        if (h->aggp_only) return 1;  // (the caller's raw rows first)
-        return run_bucket(h, run, nkeys, force_carry);
+        // a value the fixed point cannot hold exactly (or a chunk too dense): the batch
+        // again in the caller's next mode, the post-pass adding instead. The refusal
+        // sticks to the handle: data that fails the fixed-point test once (a price such
+        // as 12.34) fails it in every batch, and each refused attempt costs a whole
+        // bucketed pipeline
+        h->aggp_refused = res->refused = true;
+        return 1;
     }
-    if (flag) return 1;
-    run->out_count = total;
-    if (total > run->out_capacity) return fail(h, SH_E_MORE, "output capacity too small");
-    if (run->d_out_query && total > 0) hipMemsetAsync(run->d_out_query, 0, total * 4, st);
-    hipEventElapsedTime(&h->times.segment_ms, h->ev[0], h->ev[1]);
-    hipEventElapsedTime(&h->times.advance_ms, h->ev[1], h->ev[2]);
-    hipEventElapsedTime(&h->times.emit_ms, h->ev[2], h->ev[3]);
-    hipEventElapsedTime(&h->times.total_ms, h->ev[0], h->ev[3]);
-    h->times.advance_launches = 1;
-    h->bk_last = 1;
-    h->bk_agg_carried = carry;
-    if (carry) h->agg_last = AG.parallel ? 5 : 4;
-    return hipStreamSynchronize(st) == hipSuccess ? SH_OK : fail(h, SH_E_HIP, "bucket engine");
+    const int rc = bk_close(h, run, flag, total, &h->bk_last, "bucket engine");
+    if (h->bk_last && carry) {
+        res->carried = mode;
+        h->agg_last = AG.parallel ? 5 : 4;
+    }
+    return rc;
 }
 
 // the rise-and-fall sequence on the bucket-carry engine (sh_bucket.hip k_s3b):
@@ -1287,20 +1248,20 @@ int run_s3b(sh_handle* h, sh_device_run* run, int32_t nkeys) {
         type_width(h->stream_types[0][A]) != 4 || Q.s3_a3 != A || Q.s3_e1a != A || Q.s3_la != A || Q.s3_t3 != ty ||
         Q.s3_e1t != ty || Q.s3_lt != ty)
         return 1;
-    shb_out O;
-    memset(&O, 0, sizeof(O));
+    shb_out O{};
     O.n_out = Q.n_out;
-    shb_s3 S;
-    memset(&S, 0, sizeof(S));
+    shb_s3 S{};
     S.type = ty;
     S.warm = 1;  // (the next chunk's gather overlaps the walk: 3.42 vs 3.52 ms, profiles/r4_c3_s3b_warm_ab.txt)
     S.op2 = Q.s3_op2;
     S.dom2 = Q.s3_dom2;
     S.op3 = Q.s3_op3;
     S.dom3 = Q.s3_dom3;
+    int ms_of[SHB_MAX_OUT];
     for (int o = 0; o < Q.n_out; o++) {
         if (Q.s3_out_attr[o] != A || Q.s3_out_type[o] != ty) return 1;
         O.type[o] = ty;
+        ms_of[o] = -1;
         const int sl = Q.s3_out_slot[o];
         if (sl == 2) {
             O.kind[o] = 1;
@@ -1311,24 +1272,12 @@ int run_s3b(sh_handle* h, sh_device_run* run, int32_t nkeys) {
         while (m < S.n_ms && S.ms_slot[m] != sl) m++;
         if (m == S.n_ms) S.ms_slot[S.n_ms++] = sl;
         O.kind[o] = 0;
-        O.src[o] = (const void*)(intptr_t)m;  // resolved below
+        ms_of[o] = m;
     }
-    hipStream_t st = h->stream;
-    shb_plan B;
-    memset(&B, 0, sizeof(B));
-    B.n = run->n;
-    B.nt = (int32_t)((run->n + SHB_TILE - 1) / SHB_TILE);
-    B.et1 = B.nt;
-    B.kb = kb;
-    B.no_ts = 1;
+    shb_plan B{};
+    if (const int wrc = bk_workspace(h, run, kb, false, "sequence workspace", &B)) return wrc;
     const int64_t slots = (int64_t)B.nt * SHB_TILE;
-    if (ensure_ws(h, (int64_t)B.nt + 1) || h->bk_w0.ensure_fresh(slots * 4) || h->bk_sp.ensure_fresh(run->n * 2) ||
-        h->bk_toff.ensure_fresh((int64_t)B.nt * SHB_TOFF * 2) || h->bk_cnt.ensure_fresh(slots) ||
-        h->bk_mstart.ensure_fresh((int64_t)B.nt * SHB_NB * 4) || h->bk_tpre.ensure_fresh((int64_t)B.nt * 8) ||
-        h->bk_tfirst.ensure_fresh((int64_t)B.nt * 8) || h->bk_hstart.ensure_fresh((int64_t)B.nt * 4) ||
-        h->bk_ttot.ensure_fresh(((int64_t)B.nt + 1) * 4) || h->bk_flag.ensure_fresh(64) || h->bk_rd.ensure(64) ||
-        h->bk_st[0].ensure_fresh(slots * 4))
-        return fail(h, SH_E_OOM, "sequence workspace");
+    if (h->bk_st[0].ensure_fresh(slots * 4)) return fail(h, SH_E_OOM, "sequence workspace");
     B.n_staged = 1;
     B.st_src[0] = run->d_cols[A];
     B.st_dst[0] = h->bk_st[0].p;
@@ -1341,70 +1290,105 @@ int run_s3b(sh_handle* h, sh_device_run* run, int32_t nkeys) {
         B.ms_width[m] = 4;
     }
     for (int o = 0; o < O.n_out; o++)
-        if (O.kind[o] == 0) O.src[o] = B.ms[(int)(intptr_t)O.src[o]];
+        if (ms_of[o] >= 0) O.src[o] = B.ms[ms_of[o]];
     shb_cols OC;
-    memset(&OC, 0, sizeof(OC));
-    {
-        int32_t wd[SHB_MAX_OUT];
-        for (int o = 0; o < O.n_out; o++) wd[o] = 4;
-        direct_layout(h, run, wd, O.n_out, &OC);
-    }
-    B.ts = run->d_ts;
-    B.keys = run->d_keys;
-    B.w0 = h->bk_w0.as<uint32_t>();
-    B.sp = h->bk_sp.as<uint16_t>();
-    B.toff = h->bk_toff.as<uint16_t>();
-    B.tstride = (B.nt + 63) & ~63;
-    if (h->bk_tofft.ensure_fresh((int64_t)(SHB_NB + 1) * B.tstride * 2)) return fail(h, SH_E_OOM, "bucket workspace");
-    B.tofft = h->bk_tofft.as<uint16_t>();
-    B.cnt = h->bk_cnt.as<uint8_t>();
-    B.mstart = h->bk_mstart.as<uint32_t>();
-    B.tpre = h->bk_tpre.as<int64_t>();
-    B.tfirst = h->bk_tfirst.as<int64_t>();
-    B.hstart = h->bk_hstart.as<int32_t>();
-    B.ttot = h->bk_ttot.as<uint32_t>();
-    B.flag = h->bk_flag.as<int32_t>();
-    B.ms_ctr = h->bk_flag.as<uint32_t>() + 4;
-    static const bool prof = getenv("SH_BK_PROFILE") != nullptr;
-    if (prof) {
-        if (h->bk_prof.ensure_fresh(128)) return fail(h, SH_E_OOM, "profile");
-        hipMemsetAsync(h->bk_prof.p, 0, 128, st);
-        B.prof = h->bk_prof.as<unsigned long long>();
-    }
-    hipEventRecord(h->ev[0], st);
-    hipMemsetAsync(B.flag, 0, 32, st);
-    hipMemsetAsync(B.ttot, 0, ((int64_t)B.nt + 1) * 4, st);
-    if (shb_partition(run->d_keys, run->d_ts, nkeys, &B, st)) return fail(h, SH_E_HIP, "sequence partition failed");
-    hipEventRecord(h->ev[1], st);
+    int32_t wd[SHB_MAX_OUT];
+    for (int o = 0; o < O.n_out; o++) wd[o] = 4;
+    direct_layout(h, run, wd, O.n_out, &OC);
+    hipStream_t st = h->stream;
+    if (const int brc = bk_begin(h, run, nkeys, &B, "sequence partition failed")) return brc;
     if (shb_s3_carry(&B, &S, st)) return fail(h, SH_E_HIP, "sequence carry launch failed");
     if (shb_finish(&B, h->w_scan.as<uint32_t>(), st)) return fail(h, SH_E_HIP, "sequence scan failed");
     hipEventRecord(h->ev[2], st);
     if (shb_emit(&B, &O, &OC, 0, run->d_out_seq, run->d_out_values, run->out_capacity, st))
         return fail(h, SH_E_HIP, "sequence emit failed");
-    hipEventRecord(h->ev[3], st);
-    hipMemcpyAsync(h->bk_rd.as<void>(0), B.flag, 4, hipMemcpyDeviceToHost, st);
-    hipMemcpyAsync(h->bk_rd.as<void>(8), B.ttot + B.nt, 4, hipMemcpyDeviceToHost, st);
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(h, SH_E_HIP, "device error in the sequence engine");
-    const int32_t flag = *h->bk_rd.as<int32_t>(0);
-    const int64_t total = *h->bk_rd.as<uint32_t>(8);
+    int32_t flag = 0;
+    int64_t total = 0;
+    if (const int erc = bk_end(h, &B, "device error in the sequence engine", &flag, &total)) return erc;
     if (B.prof) {
         unsigned long long pr[16];
         hipMemcpy(pr, B.prof, 128, hipMemcpyDeviceToHost);
         fprintf(stderr, "[k_s3b clock ticks, sum over workgroups] tables+load %llu sort %llu carry %llu out %llu\n",
                 pr[0], pr[1], pr[2], pr[3]);
     }
-    if (flag & SHB_F_KEY) return fail(h, SH_E_INVALID_ARG, "partition key id >= n_keys");
-    if (flag) return 1;
-    run->out_count = total;
-    if (total > run->out_capacity) return fail(h, SH_E_MORE, "output capacity too small");
-    if (run->d_out_query && total > 0) hipMemsetAsync(run->d_out_query, 0, total * 4, st);
-    hipEventElapsedTime(&h->times.segment_ms, h->ev[0], h->ev[1]);
-    hipEventElapsedTime(&h->times.advance_ms, h->ev[1], h->ev[2]);
-    hipEventElapsedTime(&h->times.emit_ms, h->ev[2], h->ev[3]);
-    hipEventElapsedTime(&h->times.total_ms, h->ev[0], h->ev[3]);
+    return bk_close(h, run, flag, total, &h->s3b_last, "sequence engine");
+}
+
+// the window engine (sh_window.hip): the key segments, the matcher over each key's
+// events and the ordered placement; rows and sequence numbers are raw (a caller's
+// other layout is converted afterwards). 0 ok, 1 = not applicable (more than 7
+// attributes) or timestamps decrease inside a key (the caller runs the sequential
+// per-key engine), SH_E_MORE = output capacity too small, <0 error
+int run_window(sh_handle* h, sh_device_run* run, int32_t nkeys) {
+    if (h->stream_types[0].size() > 7) return 1;
+    const shd_batch B = device_batch(h, run);
+    int64_t nm = 0;
+    const int64_t n = run->n;
+    hipStream_t st = h->stream;
+    if (ensure_ws(h, n)) return fail(h, SH_E_OOM, "workspace");
+    const int na = (int)h->stream_types[0].size();
+    const bool sorted = h->partitioned;  // unpartitioned: one segment, arrival order
+    shd_window_ws wws{};
+    if (h->v_mpos.ensure_fresh(n * 4) || h->v_flag.ensure_fresh(64) || h->v_cnts.ensure_fresh(n * 4))
+        return fail(h, SH_E_OOM, "window workspace");
+    shd_payload carry;
+    void* mid[8] = {nullptr};
+    int alias = -1;
+    if (sorted && carry_setup(h, run, &carry, mid, &alias)) return fail(h, SH_E_OOM, "window workspace");
+    wws.match_pos = h->v_mpos.as<int32_t>();
+    wws.cnt_s = h->v_cnts.as<uint32_t>();
+    wws.cnt = h->w_cnt.as<uint32_t>();
+    wws.off = h->w_off.as<uint32_t>();
+    wws.flag = h->v_flag.as<int32_t>();
+    // arrival tiles: the sorted order becomes (tile, key, arrival), so the
+    // count scatter and the ordered placement touch one tile's output window
+    // at a time (L2 / Infinity-Cache resident) instead of the whole stream
+    const int tshift = sorted ? tile_shift_for(n, nkeys) : 0;
+    hipEventRecord(h->ev[0], st);
+    shd_segment_ws ws = seg_ws(h, n);
+    const uint32_t* perm = nullptr;
+    const uint32_t* skeys = nullptr;
+    if (shd_segment_payload(&B, nkeys, &ws, st, &perm, &skeys, sorted ? &carry : nullptr, mid, tshift, 0))
+        return fail(h, SH_E_HIP, "segment launch failed");
+    shd_tiles TL{};
+    if (tshift) {
+        TL.K1 = (uint32_t)nkeys + 1;
+        TL.ntile = (uint32_t)((n + ((int64_t)1 << tshift) - 1) >> tshift);
+        TL.shift = tshift;
+        const size_t words = (size_t)TL.ntile * TL.K1;
+        if (h->v_dir.ensure_fresh(words * 8)) return fail(h, SH_E_OOM, "tile directory");
+        TL.dstart = h->v_dir.as<uint32_t>();
+        TL.dend = h->v_dir.as<uint32_t>() + words;
+        if (shd_tile_dir(skeys, n, tshift, TL.K1, TL.ntile, (uint32_t*)TL.dstart, (uint32_t*)TL.dend, st))
+            return fail(h, SH_E_HIP, "tile directory launch failed");
+    }
+    hipEventRecord(h->ev[1], st);
+    const int64_t* sts = sorted ? h->v_sts.as<int64_t>() : run->d_ts;
+    const void* scols[32];
+    for (int a = 0; a < na; a++) scols[a] = sorted ? (const void*)h->v_scol[a].p : run->d_cols[a];
+    if (alias >= 0) scols[alias] = skeys;  // the partition column in key-segment order is the sorted key
+    if (h->jit_state == 0) {
+        if (getenv("SH_DISABLE_JIT")) {
+            h->jit_state = -1;
+            h->jit_err = "disabled by SH_DISABLE_JIT";
+        } else {
+            h->jit_state = shj_window_load(&h->prog, &h->jit, &h->jit_err) == 0 ? 1 : -1;
+        }
+    }
+    int wrc = shd_window(h->d_prog.as<shp_program>(), &h->prog, &B, nkeys, perm, skeys, sts, scols, &wws,
+                         h->d_cols_desc.as<shd_cols>(), h->w_scan.as<uint32_t>(), run->d_out_seq, nullptr,
+                         run->d_out_values, nullptr, run->out_capacity, &nm, st, h->ev[2],
+                         h->jit_state == 1 ? &h->jit : nullptr, tshift ? &TL : nullptr);
+    hipEventRecord(h->ev[3], st);
+    if (hipStreamSynchronize(st) != hipSuccess) return fail(h, SH_E_HIP, "device error in window engine");
+    if (wrc < 0) return fail(h, SH_E_HIP, "window engine launch failed");
+    run->out_count = nm;
+    if (wrc == 2) return fail(h, SH_E_MORE, "output capacity too small");
+    if (wrc == 1) return 1;  // timestamps decrease inside a key
+    if (run->d_out_query && nm > 0) hipMemsetAsync(run->d_out_query, 0, nm * 4, st);
+    phase_times(h);
     h->times.advance_launches = 1;
-    h->s3b_last = 1;
-    return hipStreamSynchronize(st) == hipSuccess ? SH_OK : fail(h, SH_E_HIP, "sequence engine");
+    return SH_OK;
 }
 
 // typed output columns requested: engines that write raw rows write them into a

@@ -24,6 +24,7 @@
 #include "../../include/siddhi_hip.h"
 #include "sh_agg.h"
 #include "sh_agg_seq.h"
+#include "sh_bucket_plan.h"
 #include "sh_device.h"
 #include "sh_jit.h"
 #include "sh_jmap.h"
@@ -110,19 +111,9 @@ struct PinBuf {
     }
 };
 
-inline int type_width(int t) {
-    switch (t) {
-        case SH_T_LONG:
-        case SH_T_DOUBLE: return 8;
-        case SH_T_BOOL: return 1;
-        default: return 4;
-    }
-}
-
 }  // namespace shh
 using shh::DevBuf;
 using shh::PinBuf;
-using shh::type_width;
 
 #define SH_HP_N 12
 // one k_nfa_run launch of the general engine: what its completion and any replay
@@ -252,7 +243,6 @@ struct sh_handle {
     bool kstate_stale = false;          // key blocks not reset after a k_seq3 run (reset before the next use)
     int s3_type = 0;                    // their values' type (one 4-byte attribute)
     uint64_t s3_seq_base = 0;           // and the run's first trigger sequence number
-    bool no_seq3 = false;               // rerun without k_seq3 (aggregates not exact in parallel)
     // scheduler maps' iteration order (sh_jmap.h): host models fed by the
     // launches' getState history, per-key ranks uploaded for the due-key pick
     bool sm_on = false;
@@ -311,7 +301,6 @@ struct sh_handle {
     bool r_aggp = false;                 // every rule aggregates (sh_agg.hip post-pass)
     int32_t r_agg[SHP_MAX_OUT] = {0}, r_argt[SHP_MAX_OUT] = {0};
     DevBuf a_q;                          // query per row when the caller wants none
-    bool skip_rules = false;             // rerun on the general engine (aggregates not exact in parallel)
     std::vector<int64_t> r_ixval;
     std::vector<uint32_t> r_ixstart, r_ixrule, r_free;
     std::vector<int8_t> r_ixterm;  // per rule: the f1 term its index group implies (-1: none)
@@ -370,7 +359,6 @@ struct sh_handle {
     std::string bk_err;
     DevBuf bk_w0, bk_sp, bk_toff, bk_tofft, bk_tpfx, bk_tpfb, bk_cnt, bk_mstart, bk_tpre, bk_tfirst, bk_hstart, bk_ttot, bk_flag, bk_prof;
     DevBuf bk_st[SHB_MAX_STAGED], bk_ms[SHB_MAX_MS], bk_agg[SHB_MAX_AGG];
-    bool bk_agg_carried = false;  // the last bucketed run carried its aggregates (k_bk_aggc)
     PinBuf bk_rd;
     // run_bucket's pipeline over time segments: the emitters' stream and one event per
     // matcher segment ([SH_BK_SEGS]: the emitters' end), made by the first segmented run
@@ -378,7 +366,6 @@ struct sh_handle {
     hipStream_t bk_side = nullptr;
     hipEvent_t bk_ev[SH_BK_SEGS + 1] = {};
     bool aggp_refused = false;  // run_bucket: k_bk_aggp refused a value once: the post-pass from then on
-    bool aggp_only = false;  // run_bucket: k_bk_aggp or nothing (1), the caller's layout kept
     // typed output columns (sh_device_run.d_out_cols) for engines that write rows
     DevBuf w_colrows;
     bool cols_rows = false;
@@ -438,9 +425,17 @@ int nf_settle(sh_handle* h);
 int nf_app_pull(sh_handle* h);
 int nf_ensure_keys(sh_handle* h, int32_t nkeys);
 int nf_next_due(sh_handle* h, int64_t* out);
+struct NfOpts {                // nf_process's optional arguments
+    bool fresh = false;        // sh_run_device: fresh key state, the events arriving as send() calls
+    int64_t batch_events = 0;  // of batch_events each; and then
+    bool seq3 = false;         // the rise-and-fall engine k_seq3 takes the run (the caller's test: nf_takes_seq3)
+    const sh_device_run* carry_run = nullptr;
+    const uint32_t* gidx = nullptr;
+    int64_t n_idx = 0;
+};
+bool nf_takes_seq3(const sh_handle* h);  // a single rise-and-fall query and no SH_NO_SEQ3 (read per call)
 int nf_process(sh_handle* h, const shd_batch& B, int32_t nkeys, const nf_cols& cols_in, uint64_t* d_seq,
-               int64_t* d_vals, int64_t cap, int64_t* n_rows, bool fresh = false, int64_t batch_events = 0,
-               const sh_device_run* carry_run = nullptr, const uint32_t* gidx = nullptr, int64_t n_idx = 0);
+               int64_t* d_vals, int64_t cap, int64_t* n_rows, const NfOpts& o = NfOpts());
 int nf_push(sh_handle* h, const sh_batch* b, int64_t r0, const uint32_t* index = nullptr, int64_t call_n = 0,
             int64_t call_last = 0);
 int nf_sev_flush(sh_handle* h);
@@ -460,7 +455,17 @@ int rows_for_cols(sh_handle* h, sh_device_run* run);
 // the caller's layout for an engine that writes it itself (typed columns /
 // packed rows, unless the rows were sent to the workspace): OC->use = SHB_OUT_RAW otherwise
 void direct_layout(sh_handle* h, sh_device_run* run, const int32_t* widths, int n_out, shb_cols* OC);
-int run_bucket(sh_handle* h, sh_device_run* run, int32_t nkeys, bool force_carry = false);
+shd_batch device_batch(const sh_handle* h, const sh_device_run* run);  // sh_run_device's events, arrival order
+void phase_times(sh_handle* h);
+// how run_bucket forms an aggregating select's running values: the rows carry the
+// arguments for the post-pass (agg_post), parallel carry k_bk_aggp, sequential carry k_bk_aggc
+enum BkAgg { BK_AGG_ROWS = 0, BK_AGG_PAR, BK_AGG_SEQ };
+struct BkRun {                    // ... and what it answered
+    BkAgg carried = BK_AGG_ROWS;  // the carry that formed the values (rows: none did)
+    bool refused = false;         // k_bk_aggp refused a value on the device (SHB_F_AGG)
+};
+int run_bucket(sh_handle* h, sh_device_run* run, int32_t nkeys, BkAgg mode, BkRun* res);
+int run_window(sh_handle* h, sh_device_run* run, int32_t nkeys);
 int run_rules(sh_handle* h, sh_device_run* run);
 int rules_stage(sh_handle* h, const sh_batch* b);
 int rules_step(sh_handle* h);

@@ -657,15 +657,22 @@ static int nf_place(sh_handle* h, int64_t n_idx, int64_t* rows_out, uint64_t* d_
     return SH_OK;
 }
 
+// a fresh run of this app takes the rise-and-fall engine k_seq3 (SH_NO_SEQ3: read per call)
+bool nf_takes_seq3(const sh_handle* h) { return h->T->n_queries == 1 && h->T->q[0].s3 && !getenv("SH_NO_SEQ3"); }
+
 // one or more send() calls resident on the device, processed by k_nfa_run
 
-// `carry` (sh_run_device, single stream): ts and the stream-0 columns are moved
+// `carry_run` (sh_run_device, single stream): ts and the stream-0 columns are moved
 // into key-segment order by the segment, so each lane streams its own events
 // gidx / n_idx (key-sharded push): each event's position in the whole send()
 // call of n_idx events (match counts and order tags are indexed by it)
 int nf_process(sh_handle* h, const shd_batch& B, int32_t nkeys, const nf_cols& cols_in, uint64_t* d_seq,
-                      int64_t* d_vals, int64_t cap, int64_t* n_rows, bool fresh, int64_t batch_events,
-                      const sh_device_run* carry_run, const uint32_t* gidx, int64_t n_idx) {
+               int64_t* d_vals, int64_t cap, int64_t* n_rows, const NfOpts& o) {
+    const bool fresh = o.fresh;
+    const int64_t batch_events = o.batch_events;
+    const sh_device_run* carry_run = o.carry_run;
+    const uint32_t* gidx = o.gidx;
+    int64_t n_idx = o.n_idx;
     HpScope hp_(h, 2);
     hipStream_t st = h->stream;
     const int64_t n = B.n;
@@ -686,7 +693,7 @@ int nf_process(sh_handle* h, const shd_batch& B, int32_t nkeys, const nf_cols& c
     const bool sorted_cols = carry_run && B.keys && h->stream_types[0].size() <= 7;
     // the rise-and-fall sequence engine: fresh single-query runs of that shape; its
     // device-resident rows carry no timestamps, so the segment leaves them behind
-    const bool s3_shape = fresh && h->T->n_queries == 1 && h->T->q[0].s3 && !h->no_seq3 && !getenv("SH_NO_SEQ3");
+    const bool s3_shape = fresh && o.seq3;
     const bool sorted_ts = !(s3_shape && d_seq);
     if (sorted_cols) {
         if (carry_setup(h, carry_run, &carry, mid, &alias, true, sorted_ts)) return fail(h, SH_E_OOM, "sorted columns");
@@ -1388,7 +1395,10 @@ int nf_push(sh_handle* h, const sh_batch* b, int64_t r0, const uint32_t* index, 
         int src = nf_settle(h);  // the last call's launch completes (its work overlapped this staging)
         if (src) return src;
     }
-    int rc = nf_process(h, B, nk, nf_store_cols(h), nullptr, nullptr, 0, &nrows, false, 0, nullptr, gidx, call_n);
+    NfOpts po;
+    po.gidx = gidx;
+    po.n_idx = call_n;
+    int rc = nf_process(h, B, nk, nf_store_cols(h), nullptr, nullptr, 0, &nrows, po);
     if (h->pend.on) h->pst ^= 1;
     h->seq_next += index ? call_n : n;
     h->seq_staged0 = h->seq_next;
