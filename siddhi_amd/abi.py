@@ -174,6 +174,14 @@ def bind_product(lib):
     lib.shx_seq3_status.restype = C.c_int
     lib.shx_agg_status.argtypes = [C.c_void_p]
     lib.shx_agg_status.restype = C.c_int
+    lib.shx_having_status.argtypes = [C.c_void_p]
+    lib.shx_having_status.restype = C.c_int
+    lib.shx_having_rows.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.shx_having_rows.restype = C.c_int
+    lib.shx_having_ms.argtypes = [C.c_void_p]
+    lib.shx_having_ms.restype = C.c_double
+    lib.shx_fingerprint.argtypes = [C.c_void_p]
+    lib.shx_fingerprint.restype = C.c_uint64
     lib.shx_rules_status.argtypes = [C.c_void_p]
     lib.shx_rules_status.restype = C.c_int
     lib.shx_rules_carry.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]

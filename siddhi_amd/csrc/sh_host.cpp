@@ -389,29 +389,49 @@ static int lower_chain(sh_handle* h, const sh_app_desc* app, int qi, shp_program
     return SH_OK;
 }
 
-// having / order by / limit / offset / output rate limiting need the selector pass of
-// the general engine
-static bool has_selector_extras(const sh_app_desc* app) {
+// order by / limit / offset / output rate limiting / group by, List outputs and a
+// `having` that reads a state-event attribute need the selector pass of the general
+// engine (2). A `having` over output attributes and constants alone is a predicate of
+// the finished row (sh_having.h): the fast engines take the app, with the device row
+// filter behind them (1: some query has one, its programs in *progs, one per query).
+// 0: none of these
+static int selector_extras(const sh_app_desc* app, std::vector<shv_prog>* progs) {
+    int having = 0;
+    if (progs) progs->assign((size_t)std::max(0, app->n_queries), shv_prog{});
     for (int32_t q = 0; q < app->n_queries; q++) {
         const sh_query_desc& d = app->queries[q];
-        if (d.having >= 0 || d.n_order > 0 || d.limit >= 0 || d.offset >= 0 || d.rate_kind != SH_RATE_NONE ||
-            d.n_group > 0)
-            return true;
+        if (d.n_order > 0 || d.limit >= 0 || d.offset >= 0 || d.rate_kind != SH_RATE_NONE || d.n_group > 0) return 2;
         // a List output (SH_OP_MULTI_VAR) is built by the general engine's selector
         for (int32_t o = 0; o < d.n_outputs; o++)
             if (d.outputs[o].expr >= 0 && d.outputs[o].expr < d.n_exprs && d.exprs[d.outputs[o].expr].op == SH_OP_MULTI_VAR)
-                return true;
+                return 2;
+        if (d.having >= 0) {
+            shv_prog P;
+            if (getenv("SH_NO_HAVING_FILTER") || shv_lower(&d, &P)) return 2;
+            if (progs) (*progs)[q] = P;
+            having = 1;
+        }
     }
-    return false;
+    return having;
 }
 
 static int compile_chain(sh_handle* h, const sh_app_desc* app) {
     if (app->n_queries != 1) return fail(h, SH_E_UNSUPPORTED, "chain engine: one query per app");
-    if (has_selector_extras(app))
-        return fail(h, SH_E_UNSUPPORTED, "chain engine: having / order by / limit run on the general engine");
+    std::vector<shv_prog> hv;
+    const int extras = selector_extras(app, &hv);
+    if (extras == 2)
+        return fail(h, SH_E_UNSUPPORTED, "chain engine: order by / limit / a having over state-event attributes run "
+                                         "on the general engine");
     shp_program P;
     int rc = lower_chain(h, app, 0, P);
     if (rc) return rc;
+    // an output-only `having` on a window-shaped query: sh_push_batch stays on the
+    // general engine (whose selector applies it), sh_run_device takes the chain
+    // mode's rungs with the device row filter behind them (hv_chain, as has_rules
+    // does for a small rule set)
+    if (extras == 1 && !P.window_ok)
+        return fail(h, SH_E_UNSUPPORTED, "chain engine: having on a shape outside the window engines runs on the "
+                                         "general engine");
     h->prog = P;
     h->n_out = P.n_out;
     h->partitioned = app->queries[0].partition >= 0;
@@ -421,7 +441,11 @@ static int compile_chain(sh_handle* h, const sh_app_desc* app) {
     // per-key state layout
     const char* capenv = getenv("SH_PARTIAL_CAP");
     set_layout(h->lay, P, capenv ? atoi(capenv) : 32);
-
+    if (extras == 1) {
+        h->hv_on = h->hv_chain = true;
+        h->hv_progs.swap(hv);
+        return fail(h, SH_E_UNSUPPORTED, "chain engine: having streams on the general engine");
+    }
     return SH_OK;
 }
 
@@ -445,8 +469,11 @@ static int64_t ix_const_key(int type, int64_t c) {
 static int compile_rules(sh_handle* h, const sh_app_desc* app) {
     if (app->n_queries < 2 || app->n_streams != 1)
         return fail(h, SH_E_UNSUPPORTED, "rule engine: two or more queries over one stream");
-    if (has_selector_extras(app))
-        return fail(h, SH_E_UNSUPPORTED, "rule engine: having / order by / limit run on the general engine");
+    std::vector<shv_prog> hv;
+    const int extras = selector_extras(app, &hv);
+    if (extras == 2)
+        return fail(h, SH_E_UNSUPPORTED,
+                    "rule engine: order by / limit / a having over state-event attributes run on the general engine");
     const int part = app->queries[0].partition;
     std::vector<shr_rule> rules(app->n_queries);
     std::unique_ptr<sh_handle> tmp(new sh_handle());
@@ -545,6 +572,8 @@ static int compile_rules(sh_handle* h, const sh_app_desc* app) {
     h->r_rules.swap(rules);
     h->r_partitioned = part >= 0;
     h->has_rules = true;
+    h->hv_on = extras == 1;
+    h->hv_progs.swap(hv);
     return SH_OK;
 }
 
@@ -724,6 +753,9 @@ static uint64_t program_fingerprint(const sh_handle* h) {
             f = fnv1a(h->r_agg, sizeof(h->r_agg), f);
             f = fnv1a(h->r_argt, sizeof(h->r_argt), f);
         }
+        // ... and every rule's `having` program (a set without one keeps its fingerprint)
+        if (h->hv_on)
+            for (const shv_prog& P : h->hv_progs) f = fnv1a(&P, sizeof(P), f);
         return f;
     }
     f = fnv1a(&h->prog, sizeof(h->prog), f);
@@ -757,6 +789,7 @@ int sh_compile(const sh_app_desc* app, sh_handle** out) {
         const bool rules = compile_rules(h, app) == SH_OK;
         const std::string rules_err = rules ? std::string() : h->err;
         rc = compile_nfa(h, app);
+        if (rc && h->hv_chain) h->hv_on = h->hv_chain = false;
         if (rc && rules) {
             // rule sets beyond the general engine's query table: bulk path only
             rc = SH_OK;
@@ -788,6 +821,11 @@ int sh_compile(const sh_app_desc* app, sh_handle** out) {
         hipMemcpy(h->d_T.p, h->T, sizeof(nf_table), hipMemcpyHostToDevice);
     }
     if (h->has_rules && upload_rules(h)) return SH_E_OOM;
+    if (h->hv_on) {
+        if (h->hv_d_progs.ensure(h->hv_progs.size() * sizeof(shv_prog)) || h->hv_kept.ensure(64))
+            return fail(h, SH_E_OOM, "hipMalloc failed");
+        hipMemcpy(h->hv_d_progs.p, h->hv_progs.data(), h->hv_progs.size() * sizeof(shv_prog), hipMemcpyHostToDevice);
+    }
     h->stores.resize(app->n_streams);
     for (int s = 0; s < app->n_streams; s++) {
         h->stores[s].cols.resize(h->stream_types[s].size());
@@ -867,6 +905,8 @@ void sh_destroy(sh_handle* h) {
         h->rc_ws.release();
         h->rc_oq.release();
         h->rc_ots.release();
+        DevBuf* hvb[] = {&h->hv_d_progs, &h->hv_ws, &h->hv_kept, &h->hv_seq, &h->hv_q, &h->hv_ts, &h->hv_vals};
+        for (DevBuf* b : hvb) b->release();
         for (auto& st : h->stores) {
             for (auto& c : st.cols) c.release();
             for (auto& c : st.nuls) c.release();
@@ -874,6 +914,8 @@ void sh_destroy(sh_handle* h) {
         for (auto& e : h->ev)
             if (e) hipEventDestroy(e);
         for (auto& e : h->bk_ev)
+            if (e) hipEventDestroy(e);
+        for (auto& e : h->hv_ev)
             if (e) hipEventDestroy(e);
         if (h->bk_side) hipStreamDestroy(h->bk_side);
         hipStreamDestroy(h->own_stream);
@@ -1553,6 +1595,82 @@ static int run_chain(sh_handle* h, sh_device_run* run, int32_t nkeys) {
     return rc != 1 ? rc : rung_batch(h, run, nkeys);
 }
 
+// the engines of one sh_run_device call; *general: the general engine's rows stand
+// (its selector applied any `having`)
+static int run_engines(sh_handle* h, sh_device_run* run, bool* general) {
+    bool rules_seq = false;  // a rule set's aggregates left the post-pass for the general engine
+    if (h->has_rules && (h->mode == 2 || !getenv("SH_DISABLE_RULES"))) {
+        const int rrc = rung_rules(h, run);
+        if (rrc != 1) return rrc;
+        rules_seq = true;
+    }
+    if (h->mode == 1 && !h->hv_chain) {
+        *general = true;
+        return run_general(h, run, rules_seq);
+    }
+    // the chain mode, from fresh per-key state
+    const int32_t nkeys = h->partitioned ? std::max(1, run->n_keys) : 1;
+    if (ensure_keys(h, nkeys)) return fail(h, SH_E_OOM, "key state");
+    hipMemsetAsync(h->d_kstate.p, 0, (size_t)nkeys * h->lay.key_bytes, h->stream);
+    h->times = sh_kernel_times{};
+    h->agg_last = 0;
+    return run_chain(h, run, nkeys);
+}
+
+// Under an output-only `having` (h->hv_on) every rung writes raw rows, sequence
+// numbers and (for a rule set) query ids into the filter's source buffers; the
+// device row filter (sh_having.hip) then writes the kept rows where the caller's
+// rows go (its raw buffers, or the workspace the packed-row / typed-column
+// conversion reads), once, after whichever rung produced the standing rows. None of
+// the rungs knows `having`; aggregators are updated by every match, kept or not.
+static int run_device_having(sh_handle* h, sh_device_run* run) {
+    int rc = rows_for_cols(h, run);
+    if (rc) return rc;
+    const int no = std::max(1, h->n_out);
+    const size_t cap = (size_t)std::max<int64_t>(1, run->out_capacity);
+    int64_t* dst_vals = run->d_out_values;
+    uint64_t* dst_seq = run->d_out_seq;
+    int32_t* dst_q = run->d_out_query;
+    const bool want_q = dst_q != nullptr || h->hv_progs.size() > 1;
+    if (!dst_vals) return fail(h, SH_E_INVALID_ARG, "sh_run_device: d_out_values is NULL");
+    if (h->hv_vals.ensure_fresh(cap * no * 8) || h->hv_seq.ensure_fresh(cap * 8) ||
+        (want_q && h->hv_q.ensure_fresh(cap * 4)))
+        return fail(h, SH_E_OOM, "having filter buffers");
+    run->d_out_values = h->hv_vals.as<int64_t>();
+    run->d_out_seq = h->hv_seq.as<uint64_t>();
+    run->d_out_query = want_q ? h->hv_q.as<int32_t>() : nullptr;
+    bool general = false;
+    rc = run_engines(h, run, &general);
+    run->d_out_values = dst_vals;
+    run->d_out_seq = dst_seq;
+    run->d_out_query = dst_q;
+    if (rc != SH_OK) return rc;  // (a too-small out_capacity: the unfiltered count, as without `having`)
+    const int64_t m = run->out_count;
+    if (m < 0 || m > run->out_capacity) return fail(h, SH_E_HIP, "having filter: row count out of range");
+    if (general) {
+        // the general engine's selector applied `having`: its rows as they are
+        if (m > 0) {
+            hipMemcpyAsync(dst_vals, h->hv_vals.p, (size_t)m * no * 8, hipMemcpyDeviceToDevice, h->stream);
+            if (dst_seq) hipMemcpyAsync(dst_seq, h->hv_seq.p, (size_t)m * 8, hipMemcpyDeviceToDevice, h->stream);
+            if (dst_q) hipMemcpyAsync(dst_q, h->hv_q.p, (size_t)m * 4, hipMemcpyDeviceToDevice, h->stream);
+            if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(h, SH_E_HIP, "device error copying rows");
+        }
+        return SH_OK;
+    }
+    rc = having_filter(h, m, no, h->hv_seq.as<uint64_t>(), h->hv_vals.as<int64_t>(),
+                       want_q ? h->hv_q.as<int32_t>() : nullptr, nullptr, dst_seq, dst_vals, dst_q, nullptr);
+    if (rc) return rc;
+    unsigned long long kept = 0;
+    hipMemcpyAsync(&kept, h->hv_kept.p, 8, hipMemcpyDeviceToHost, h->stream);
+    if (hipStreamSynchronize(h->stream) != hipSuccess || (int64_t)kept > m)
+        return fail(h, SH_E_HIP, "device error in the having filter");
+    run->out_count = (int64_t)kept;
+    h->hv_last = 1;
+    h->hv_rows_in = m;
+    h->hv_rows_kept = (int64_t)kept;
+    return SH_OK;
+}
+
 static int run_device_impl(sh_handle* h, sh_device_run* run) {
     if (!h->has_device) return fail(h, SH_E_NO_DEVICE, "no HIP device");
     if (h->app.n_streams != 1) return fail(h, SH_E_UNSUPPORTED, "sh_run_device: single-stream apps only");
@@ -1561,20 +1679,10 @@ static int run_device_impl(sh_handle* h, sh_device_run* run) {
     // were written there (the handle's own stream is non-blocking and would not
     // wait for them)
     h->stream = (hipStream_t)run->stream;
-    bool rules_seq = false;  // a rule set's aggregates left the post-pass for the general engine
-    if (h->has_rules && (h->mode == 2 || !getenv("SH_DISABLE_RULES"))) {
-        const int rrc = rung_rules(h, run);
-        if (rrc != 1) return rrc;
-        rules_seq = true;
-    }
-    if (h->mode == 1) return run_general(h, run, rules_seq);
-    // the chain mode, from fresh per-key state
-    const int32_t nkeys = h->partitioned ? std::max(1, run->n_keys) : 1;
-    if (ensure_keys(h, nkeys)) return fail(h, SH_E_OOM, "key state");
-    hipMemsetAsync(h->d_kstate.p, 0, (size_t)nkeys * h->lay.key_bytes, h->stream);
-    h->times = sh_kernel_times{};
-    h->agg_last = 0;
-    return run_chain(h, run, nkeys);
+    h->hv_last = 0;
+    if (h->hv_on) return run_device_having(h, run);
+    bool general = false;
+    return run_engines(h, run, &general);
 }
 
 static int run_device_cols(sh_handle* h, sh_device_run* run);
@@ -1725,6 +1833,27 @@ int shx_seq3_status(sh_handle* h) { return h ? (h->s3b_last ? 2 : h->seq3_last) 
 // aggregators of the last sh_run_device: 0 none on a fast engine, 1 the post-pass
 // (sh_agg.hip) formed them, 2 it was not exact and a sequential engine ran
 int shx_agg_status(sh_handle* h) { return h ? h->agg_last : 0; }
+
+// `having` of the last sh_run_device or streaming step: 1 the device row filter
+// (sh_having.hip) applied it, 0 there is none or the general engine's selector did
+int shx_having_status(sh_handle* h) { return h ? h->hv_last : 0; }
+// ... and that filter's rows in and rows kept (0, 0 when it did not run)
+int shx_having_rows(sh_handle* h, int64_t* rows_in, int64_t* rows_kept) {
+    if (!h) return 0;
+    if (rows_in) *rows_in = h->hv_last ? h->hv_rows_in : 0;
+    if (rows_kept) *rows_kept = h->hv_last ? h->hv_rows_kept : 0;
+    return h->hv_last;
+}
+
+// device time of the last run's or step's filter launches (mark, scan, move), ms
+double shx_having_ms(sh_handle* h) {
+    float ms = 0.f;
+    if (!h || !h->hv_last || !h->hv_ev[1] || hipEventElapsedTime(&ms, h->hv_ev[0], h->hv_ev[1]) != hipSuccess) return 0.0;
+    return ms;
+}
+
+// the compiled-program fingerprint a snapshot image carries (0: no handle)
+uint64_t shx_fingerprint(sh_handle* h) { return h ? h->fp : 0; }
 
 int shx_rules_status(sh_handle* h) { return h ? h->rs_last : 0; }
 

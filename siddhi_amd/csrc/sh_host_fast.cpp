@@ -652,6 +652,23 @@ int rules_stage(sh_handle* h, const sh_batch* b) {
     return SH_OK;
 }
 
+// the device row filter (sh_having.hip) over m ordered raw rows, launched on the
+// handle's stream: the kept rows go to the o_* buffers, their count to h->hv_kept
+int having_filter(sh_handle* h, int64_t m, int n_out, const uint64_t* seq, const int64_t* vals, const int32_t* query,
+                  const int64_t* ts, uint64_t* o_seq, int64_t* o_vals, int32_t* o_query, int64_t* o_ts) {
+    if (h->hv_ws.ensure_fresh((size_t)shv_filter_ws_words(m) * 4) || h->hv_kept.ensure(64))
+        return fail(h, SH_E_OOM, "having filter workspace");
+    for (auto& e : h->hv_ev)
+        if (!e) hipEventCreate(&e);
+    hipEventRecord(h->hv_ev[0], h->stream);
+    if (shv_filter(h->hv_d_progs.as<shv_prog>(), (int32_t)h->hv_progs.size(), m, n_out, seq, vals, query, ts, nullptr,
+                   o_seq, o_vals, o_query, o_ts, nullptr, h->hv_ws.as<uint32_t>(),
+                   h->hv_kept.as<unsigned long long>(), h->stream))
+        return fail(h, SH_E_HIP, "having filter launch failed");
+    hipEventRecord(h->hv_ev[1], h->stream);
+    return SH_OK;
+}
+
 // the staged calls are dropped: a refused step leaves the handle where it was
 // before them (counters included), with the carried state untouched
 static int rules_step_fail(sh_handle* h, int code, const char* msg) {
@@ -792,6 +809,7 @@ int rules_step(sh_handle* h) {
     if (hipStreamSynchronize(st) != hipSuccess) return rules_step_fail(h, SH_E_HIP, "device error in the rule scan");
     if (flag) return rules_step_fail(h, SH_E_UNSUPPORTED, "rule engine: timestamps decrease inside a key");
     const int64_t m = (int64_t)lo + lc;
+    int64_t mk = m;  // the rows that reach the host queue (after `having`)
     // the next carried state, beside the current one
     oom = Bn.ts.ensure_fresh(std::max<size_t>(nrows, 1) * 8) | Bn.key.ensure_fresh(std::max<size_t>(nrows, 1) * 4) |
           Bn.seq.ensure_fresh(std::max<size_t>(nrows, 1) * 8) | Bn.c_off.ensure_fresh(((size_t)nrows + 1) * 4) |
@@ -850,6 +868,22 @@ int rules_step(sh_handle* h) {
                             &AD, &T, h->a_scratch.p, st, &ag_pk, &ag_fin))
                 return rules_step_fail(h, SH_E_HIP, "carried aggregate launch failed");
         }
+        // `having`: the rows handed to the host queue are the kept ones, from the
+        // filter's own buffers (the aggregate table below takes every row's state)
+        if (h->hv_on) {
+            if (h->hv_seq.ensure_fresh((size_t)m * 8) || h->hv_ts.ensure_fresh((size_t)m * 8) ||
+                h->hv_q.ensure_fresh((size_t)m * 4) || h->hv_vals.ensure_fresh((size_t)m * no * 8))
+                return rules_step_fail(h, SH_E_OOM, "having filter buffers");
+            if (having_filter(h, m, no, h->w_oseq.as<uint64_t>(), h->w_ovals.as<int64_t>(), h->rc_oq.as<int32_t>(),
+                              h->rc_ots.as<int64_t>(), h->hv_seq.as<uint64_t>(), h->hv_vals.as<int64_t>(),
+                              h->hv_q.as<int32_t>(), h->hv_ts.as<int64_t>()))
+                return rules_step_fail(h, SH_E_HIP, h->err.c_str());
+            unsigned long long kept = 0;
+            hipMemcpyAsync(&kept, h->hv_kept.p, 8, hipMemcpyDeviceToHost, st);
+            if (hipStreamSynchronize(st) != hipSuccess || (int64_t)kept > m)
+                return rules_step_fail(h, SH_E_HIP, "device error in the having filter");
+            mk = (int64_t)kept;
+        }
     } else {
         hipEventRecord(h->ev[2], st);
     }
@@ -860,17 +894,21 @@ int rules_step(sh_handle* h) {
     // rows into the host output queue; the per-key last timestamps move last, when
     // nothing can refuse the step any more
     const size_t base = h->o_seq.size();
-    h->o_query.resize(base + m);
-    h->o_seq.resize(base + m);
-    h->o_ts.resize(base + m);
-    h->o_vals.resize((base + m) * h->n_out);
-    h->o_nulls.resize((base + m) * h->n_out, 0);
-    if (m > 0) {
-        hipMemcpyAsync(h->o_query.data() + base, h->rc_oq.p, (size_t)m * 4, hipMemcpyDeviceToHost, st);
-        hipMemcpyAsync(h->o_seq.data() + base, h->w_oseq.p, (size_t)m * 8, hipMemcpyDeviceToHost, st);
-        hipMemcpyAsync(h->o_ts.data() + base, h->rc_ots.p, (size_t)m * 8, hipMemcpyDeviceToHost, st);
+    h->o_query.resize(base + mk);
+    h->o_seq.resize(base + mk);
+    h->o_ts.resize(base + mk);
+    h->o_vals.resize((base + mk) * h->n_out);
+    h->o_nulls.resize((base + mk) * h->n_out, 0);
+    if (mk > 0) {
+        const DevBuf& oq = h->hv_on ? h->hv_q : h->rc_oq;
+        const DevBuf& oseq = h->hv_on ? h->hv_seq : h->w_oseq;
+        const DevBuf& ots = h->hv_on ? h->hv_ts : h->rc_ots;
+        const DevBuf& ovals = h->hv_on ? h->hv_vals : h->w_ovals;
+        hipMemcpyAsync(h->o_query.data() + base, oq.p, (size_t)mk * 4, hipMemcpyDeviceToHost, st);
+        hipMemcpyAsync(h->o_seq.data() + base, oseq.p, (size_t)mk * 8, hipMemcpyDeviceToHost, st);
+        hipMemcpyAsync(h->o_ts.data() + base, ots.p, (size_t)mk * 8, hipMemcpyDeviceToHost, st);
         if (h->n_out)
-            hipMemcpyAsync(h->o_vals.data() + base * h->n_out, h->w_ovals.p, (size_t)m * h->n_out * 8,
+            hipMemcpyAsync(h->o_vals.data() + base * h->n_out, ovals.p, (size_t)mk * h->n_out * 8,
                            hipMemcpyDeviceToHost, st);
     }
     // ... and with them the segments' final aggregate states into their table
@@ -900,6 +938,9 @@ int rules_step(sh_handle* h) {
     h->rs_last = 0;
     if (ag_pk) h->ag_entries += (int64_t)ag_ctl[0];  // the slots this step claimed
     if (h->r_aggp) h->agg_last = 6;
+    h->hv_last = h->hv_on ? 1 : 0;
+    h->hv_rows_in = m;
+    h->hv_rows_kept = mk;
     h->rq_ts.clear();
     h->rq_key.clear();
     h->rq_seq.clear();

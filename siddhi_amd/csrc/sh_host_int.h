@@ -26,6 +26,7 @@
 #include "sh_agg_seq.h"
 #include "sh_bucket_plan.h"
 #include "sh_device.h"
+#include "sh_having.h"
 #include "sh_jit.h"
 #include "sh_jmap.h"
 #include "sh_nfa.h"
@@ -381,6 +382,17 @@ struct sh_handle {
     int agg_last = 0;  // 1: post-pass done, 2: post-pass not exact -> sequential engine, 3: in the k_seq3s lanes,
                        // 4: carried per key by the bucketed engine (k_bk_aggc), 5: ... in parallel (k_bk_aggp),
                        // 6: carried sequential pass (k_shc_walk: a rule set beyond the general engine's table)
+    // ---- output-only `having` behind the fast engines (sh_having.h / sh_having.hip):
+    // one row predicate per query (an empty program keeps every row), the device
+    // copy, the filter's workspace and its destination buffers (a streaming step
+    // hands the host queue the kept rows from them), and the last run's counts
+    bool hv_on = false;
+    bool hv_chain = false;             // a one-query window-shaped app: mode 1 to stream, the chain rungs in bulk
+    std::vector<shv_prog> hv_progs;
+    DevBuf hv_d_progs, hv_ws, hv_kept, hv_seq, hv_q, hv_ts, hv_vals;
+    int hv_last = 0;                   // 1: the device row filter ran in the last run or step
+    int64_t hv_rows_in = 0, hv_rows_kept = 0;
+    hipEvent_t hv_ev[2] = {};          // around the filter's launches (made by the first one)
     std::vector<int32_t> out_types;  // per select position over the queries (-2: types differ)
     uint64_t fp = 0;                 // compiled-program fingerprint (snapshot images)
 };
@@ -469,6 +481,10 @@ int run_window(sh_handle* h, sh_device_run* run, int32_t nkeys);
 int run_rules(sh_handle* h, sh_device_run* run);
 int rules_stage(sh_handle* h, const sh_batch* b);
 int rules_step(sh_handle* h);
+// the device row filter over m ordered rows (sources and destinations apart, query /
+// ts NULL where the path has none); the kept count lands in h->hv_kept (8 bytes)
+int having_filter(sh_handle* h, int64_t m, int n_out, const uint64_t* seq, const int64_t* vals, const int32_t* query,
+                  const int64_t* ts, uint64_t* o_seq, int64_t* o_vals, int32_t* o_query, int64_t* o_ts);
 int run_s3b(sh_handle* h, sh_device_run* run, int32_t nkeys);
 shd_segment_ws seg_ws(sh_handle* h, int64_t n);
 int tile_shift_for(int64_t n, int32_t nkeys);
@@ -480,6 +496,10 @@ int shx_jit_compile(sh_handle* h);
 int shx_bucket_status(sh_handle* h);
 int shx_seq3_status(sh_handle* h);
 int shx_agg_status(sh_handle* h);
+int shx_having_status(sh_handle* h);
+int shx_having_rows(sh_handle* h, int64_t* rows_in, int64_t* rows_kept);
+double shx_having_ms(sh_handle* h);
+uint64_t shx_fingerprint(sh_handle* h);
 int shx_rules_status(sh_handle* h);
 int shx_rules_carry(sh_handle* h, int64_t* partials, int64_t* rows);
 int shx_rules_agg_carry(sh_handle* h, int64_t* entries);

@@ -193,6 +193,21 @@ class DeviceRunner:
         streaming step, and a bulk run whose additions would round), 0 none."""
         return lib().shx_agg_status(self.handle.h)
 
+    def having_status(self):
+        """1: the device row filter (sh_having.hip) applied the output-only `having`
+        of the last run, 0: there is none, or the general engine's selector did."""
+        return lib().shx_having_status(self.handle.h)
+
+    def having_rows(self):
+        """(rows in, rows kept) of the device row filter in the last run"""
+        a, b = C.c_int64(0), C.c_int64(0)
+        lib().shx_having_rows(self.handle.h, C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def having_ms(self):
+        """device time of the last run's filter launches (mark, scan, move), ms"""
+        return lib().shx_having_ms(self.handle.h)
+
     def last_error(self):
         return lib().sh_last_error(self.handle.h).decode()
 
