@@ -1006,8 +1006,7 @@ static int bk_workspace(sh_handle* h, const sh_device_run* run, int kb, bool mat
     B->ttot = h->bk_ttot.as<uint32_t>();
     B->flag = h->bk_flag.as<int32_t>();
     B->ms_ctr = h->bk_flag.as<uint32_t>() + 4;
-    static const bool prof = getenv("SH_BK_PROFILE") != nullptr;
-    if (prof) {
+    if (shj_bucket_profiled()) {
         if (h->bk_prof.ensure_fresh(128)) return fail(h, SH_E_OOM, "profile");
         hipMemsetAsync(h->bk_prof.p, 0, 128, h->stream);
         B->prof = h->bk_prof.as<unsigned long long>();

@@ -944,75 +944,98 @@ bool gen_bucket(const shp_program& P, const ExtForm& F, const std::vector<int>& 
     auto walk_count_f_dyn = [&]() {
         const bool mx = F.op == SH_OP_GT || F.op == SH_OP_GE;
         const std::string opn = std::to_string(F.op);
-        const std::string ext = F.dom == DOM_F32 ? (mx ? "__builtin_fmaxf" : "__builtin_fminf")
-                                                 : (mx ? "__builtin_fmax" : "__builtin_fmin");
         const std::string nan = F.dom == DOM_F32 ? "__builtin_nanf(\"\")" : "__builtin_nan(\"\")";
         std::string cand_f = "bool ok = true;\n" + unguard(gq.terms(F.f1, "ok")) + unguard(gq.terms(F.ionly, "ok")) +
                              "{\n" + unguard(gq.yval(F, "y")) + "ok = ok && cmp_op<" + DT + ">(" + opn +
                              ", xq, y) && !cmp_op<" + DT + ">(" + opn + ", Mx, y);\n}\n";
+        // (the running extreme as a select: xr replaces Mx when it beats it or Mx is still
+        // NaN, a NaN xr never does -- maxNum / minNum's result wherever a compare sees it)
         std::string mid_f = "bool mk = true;\n" + unguard(gi.terms(F.qonly, "mk")) + "{\n" + unguard(gi.xval(F, "xr")) +
-                            "Mx = (act && mk) ? " + ext + "(Mx, xr) : Mx;\n}\n";
+                            "Mx = (act & (uint32_t)(mk & ((xr " + (mx ? ">" : "<") + " Mx) | (Mx != Mx)))) ? xr : Mx;\n}\n";
+        // one iteration is two LDS round trips: the hand-out's s_cons word, then the new
+        // consumer's own words together with the block's SHB_D predecessor words (pp: the
+        // block's first predecessor, sp - 1 for a new consumer, below 0 once a walk has
+        // left the span: loads below the span clamp to element 0). The premise flags
+        // collect in a register (flg_) and go out once per wave after the loop; the
+        // timestamp-order check rides on step 0 of a consumer's first block, which reads
+        // the word it needs (tmono_: the consumer's word with every key bit set for that
+        // block, the maximum after). Times compare in place, as packed words: w >> kb >= tlo
+        // is w >= tlo << kb. call_ counts the partials taken; one at step >= SHB_MSTEPS
+        // lands on the mask's bit 15, SHB_MOVF
         std::string s =
             "{\n"
             "const int dl_ = (int)(threadIdx.x & 63u), dw_ = (int)(threadIdx.x >> 6);\n"
             "const int per_ = (nc + (SHB_TPB / 64) - 1) / (SHB_TPB / 64);\n"
             "const int c0_ = dw_ * per_ < nc ? dw_ * per_ : nc, c1_ = c0_ + per_ < nc ? c0_ + per_ : nc;\n"
             "const uint64_t dlt_ = dl_ ? (~0ull >> (64 - dl_)) : 0ull;\n"
-            "int next_ = c0_, ci = -1, sp = 0, i = 0, base = 0;\n"
-            "uint32_t wq = 0u, tlo = 0u, mask = 0u, cext = 0u, roff = 0u, live = 0u;\n" +
+            "int next_ = c0_, ci = -1, ia_ = 0, base = 0, pp = 0;\n"
+            "uint32_t wq = 0u, tlo = 0u, tmono_ = ~0u, mask = 0u, call_ = 0u, roff = 0u, live = 0u, flg_ = 0u;\n" +
             DT + " xq = 0;\n" + DT + " Mx = " + nan + ";\n"
             "for (;;) {\n"
             "    if (ci >= 0 && !live) {\n"
-            "        const uint32_t c_ = (uint32_t)__popc(mask & ~SHB_MOVF) + cext;\n"
-            "        if (roff && SHB_OFF(wq >> kb)) atomicOr(P.flag, SHB_F_HALO);\n"
-            "        if (c_ > 255u) atomicOr(P.flag, SHB_F_COUNT);\n"
-            "        s_pre[i - hl] = (uint16_t)(c_ > 255u ? 255u : c_);\n"
-            "        s_msk[i - hl] = (uint16_t)mask;\n"
+            "        if (roff && SHB_OFF(wq >> kb)) flg_ |= (uint32_t)SHB_F_HALO;\n"
+            "        if (call_ > 255u) flg_ |= (uint32_t)SHB_F_COUNT;\n"
+            "        s_pre[ia_] = (uint16_t)(call_ > 255u ? 255u : call_);\n"
+            "        s_msk[ia_] = (uint16_t)mask;\n"
             "        slow_ |= (int)(mask & SHB_MOVF);\n"
             "        ci = -1;\n"
             "    }\n"
             "    const uint64_t im_ = __ballot(ci < 0);\n"
             "    const int r_ = (int)__popcll(im_ & dlt_);\n"
-            "    if (ci < 0 && next_ + r_ < c1_) {\n"
-            "        ci = next_ + r_;\n"
-            "        const uint32_t cw = s_cons[ci];\n"
-            "        sp = (int)(cw & 0xFFFFu);\n"
-            "        i = hl + (int)(cw >> 16);\n"
-            "        wq = s_ws[sp];\n"
-            "        const uint32_t tq32 = wq >> kb;\n"
-            "        tlo = tq32 > SHB_WLIM ? tq32 - SHB_WLIM : 0u;\n" +
-            decl_attrs(need_q, 1) + loads(need_q, "x1_", "sp") + "xq = 0;\n" + qhead +
-            "        Mx = " + nan + ";\n"
-            "        mask = 0u; cext = 0u; roff = 0u; base = 0;\n"
-            "        live = (qok && xq == xq) ? 1u : 0u;\n"
-            "        if (live && sp >= 1) {\n"
-            "            const uint32_t wp = s_ws[sp - 1];\n"
-            "            if (((wp ^ wq) & kmask) == 0u && (wp >> kb) > tq32) atomicOr(P.flag, SHB_F_MONO);\n"
-            "        }\n"
-            "    }\n"
+            "    const bool take_ = ci < 0 && next_ + r_ < c1_;\n"
+            "    if (take_) ci = next_ + r_;\n"
             "    next_ += (int)__popcll(im_);\n"
             "    if (__ballot(ci >= 0) == 0ull) break;\n"
-            "    uint32_t wv[SHB_D];\n";
+            "    const uint32_t cw = s_cons[take_ ? ci : 0];\n"
+            "    const int sq_ = take_ ? (int)(cw & 0xFFFFu) : 0;\n"
+            "    if (take_) { pp = sq_ - 1; base = 0; ia_ = (int)(cw >> 16); }\n"
+            "    const uint32_t wl_ = s_ws[sq_];\n";
+        for (int a : need_q)
+            s += "    const " + std::string(col_ctype(P.attr_type[0][a])) + " rq" + std::to_string(a) + " = " + lds(a) + "[sq_];\n";
+        s += "    uint32_t wv[SHB_D];\n";
         for (int a : need_r)
             s += std::string(col_ctype(P.attr_type[0][a])) + " av" + std::to_string(a) + "[SHB_D];\n";
-        s += "#pragma unroll\nfor (int u = 0; u < SHB_D; u++) {\n    const int o0 = sp - 1 - base - u;\n"
-             "    const int o = o0 < 0 ? 0 : o0;\n    wv[u] = s_ws[o];\n";
+        s += "#pragma unroll\nfor (int u = 0; u < SHB_D; u++) {\n"
+             "    const int o = pp - u < 0 ? 0 : pp - u;\n"
+             "    wv[u] = s_ws[o];\n";
         for (int a : need_r) s += "    av" + std::to_string(a) + "[u] = " + lds(a) + "[o];\n";
-        s += "}\n" + decl_attrs(need_r, 0) +
+        s += "}\n"
+             "    if (take_) {\n"
+             "        wq = wl_;\n"
+             "        const uint32_t tq32 = wq >> kb;\n"
+             "        tlo = (tq32 > SHB_WLIM ? tq32 - SHB_WLIM : 0u) << kb;\n"
+             "        tmono_ = wq | kmask;\n" +
+             decl_attrs(need_q, 1);
+        for (int a : need_q)
+            s += "x1_" + std::to_string(a) + " = " + raw_of(P.attr_type[0][a], "rq" + std::to_string(a)) + ";\n";
+        s += "xq = 0;\n" + qhead +
+             "        Mx = " + nan + ";\n"
+             "        mask = 0u; call_ = 0u; roff = 0u;\n"
+             "        live = (qok && xq == xq) ? 1u : 0u;\n"
+             "    }\n" +
+             decl_attrs(need_r, 0) +
              "#pragma unroll\nfor (int u = 0; u < SHB_D; u++) {\n"
              "    const int step = base + u;\n"
-             "    const uint32_t same = (u < sp - base && ((wv[u] ^ wq) & kmask) == 0u) ? 1u : 0u;\n"
+             "    const uint32_t same = (u <= pp && ((wv[u] ^ wq) & kmask) == 0u) ? 1u : 0u;\n"
              "    roff |= live & (same ^ 1u);\n"
-             "    const uint32_t act = live & same & ((wv[u] >> kb) >= tlo ? 1u : 0u);\n";
+             "    if (u == 0) flg_ |= (live & same & (wv[u] > tmono_ ? 1u : 0u)) ? (uint32_t)SHB_F_MONO : 0u;\n"
+             "    const uint32_t act = live & same & (wv[u] >= tlo ? 1u : 0u);\n";
         for (int a : need_r)
             s += "    x0_" + std::to_string(a) + " = " + raw_of(P.attr_type[0][a], "av" + std::to_string(a) + "[u]") + ";\n";
         s += "    {\n" + cand_f +
              "    const uint32_t cons = act & (ok ? 1u : 0u);\n"
-             "    if (step < SHB_MSTEPS) mask |= cons << step;\n"
-             "    else { cext += cons; mask |= cons ? SHB_MOVF : 0u; }\n    }\n";
+             "    call_ += cons;\n"
+             "    mask |= cons << (step < SHB_MSTEPS ? step : SHB_MSTEPS);\n    }\n";
         s += "    {\n" + mid_f + "    }\n    live = act & (cmp_op<" + DT + ">(" + (mx ? std::to_string(SH_OP_GE)
                                                                                   : std::to_string(SH_OP_LE)) +
-             ", Mx, xq) ? 0u : 1u);\n}\nbase += SHB_D;\n}\n}\n";
+             ", Mx, xq) ? 0u : 1u);\n}\ntmono_ = ~0u;\nbase += SHB_D;\npp -= SHB_D;\n"
+             "}\n"
+             "if (__ballot(flg_ != 0u) != 0ull) {\n"
+             "    const uint32_t f_ = (__ballot((flg_ & SHB_F_HALO) != 0u) ? (uint32_t)SHB_F_HALO : 0u) |\n"
+             "                        (__ballot((flg_ & SHB_F_COUNT) != 0u) ? (uint32_t)SHB_F_COUNT : 0u) |\n"
+             "                        (__ballot((flg_ & SHB_F_MONO) != 0u) ? (uint32_t)SHB_F_MONO : 0u);\n"
+             "    if (dl_ == 0) atomicOr(P.flag, (int)f_);\n"
+             "}\n}\n";
         return s;
     };
     auto walk = [&](bool count, const std::string& on_consumed) {
@@ -1025,12 +1048,16 @@ bool gen_bucket(const shp_program& P, const ExtForm& F, const std::vector<int>& 
                   "])[dst] = " + lds(a) + "[o];\n";
     }
     (void)sidx;
+    // the phase clocks (SH_BK_PROFILE) are generated only when asked for: the
+    // production kernel reads no clock and carries no t_prev
+    const bool prof = shj_bucket_profiled() != 0;
+    auto phase = [&](int ph) { return prof ? "SHB_PROF(" + std::to_string(ph) + ")\n" : std::string(); };
 
     src = SHJ_HEADERS;
     const int64_t wlim = P.within_ms < 0 ? 0 : (P.within_ms > 0xFFFFFFFFll ? 0xFFFFFFFFll : P.within_ms);
     src += "\n#define SHJ_W " + lit64(P.within_ms) + "\n#define SHB_WLIM " + std::to_string(wlim) +
            "u\n#define SHB_TPB 512\n#define SHB_D " + std::to_string(kWalkBlock) +
-           "\n#define SHB_MOVF 0x8000u\n#define SHB_MSTEPS 15\n"
+           "\n#define SHB_MOVF 0x8000u\n#define SHB_MSTEPS 15\nstatic_assert(SHB_MOVF == 1u << SHB_MSTEPS, \"mask\");\n"
            "#define SHB_MINB " + std::to_string(kMatchMinBlocks) + "\n"
            "#define SHB_NSEG (SHB_CT_MAX + SHB_HMAX)\n"
            "#define SHB_SPANJ " + std::to_string(kSpan) + "\n#define SHB_CHJ " + std::to_string(kChunk) + "\n" +
@@ -1084,8 +1111,9 @@ const int E = A + P.ct < P.nt ? A + P.ct : P.nt;
 const int kb = P.kb;
 const uint32_t kmask = (1u << kb) - 1u;
 const int lane = (int)(threadIdx.x & 63u), wv = (int)(threadIdx.x >> 6);
-unsigned long long t_prev = wall_clock64();  // (the table load counts with the first pass's table phase)
-const int T0 = A - SHB_HMAX;  // the table's first tile (entries of tiles < 0 are never read)
+)";
+    if (prof) src += "unsigned long long t_prev = wall_clock64();  // (the table load counts with the first pass's table phase)\n";
+    src += R"(const int T0 = A - SHB_HMAX;  // the table's first tile (entries of tiles < 0 are never read)
 {
     const int Tm = T0 + (int)threadIdx.x;
     if (Tm >= 0 && Tm <= E) {
@@ -1101,9 +1129,12 @@ const int T0 = A - SHB_HMAX;  // the table's first tile (entries of tiles < 0 ar
 }
 for (int a = A; a < E;) {
 __syncthreads();
-if (a != A) t_prev = wall_clock64();
-#define SHB_PROF(ph) if (P.prof && threadIdx.x == 0) { const unsigned long long t_now = wall_clock64(); atomicAdd(&P.prof[ph], t_now - t_prev); t_prev = t_now; }
-// the pass's segments, one per tile from the first halo tile h0: seg_p[t] the
+)";
+    if (prof)
+        src += "if (a != A) t_prev = wall_clock64();\n"
+               "#define SHB_PROF(ph) if (P.prof && threadIdx.x == 0) { const unsigned long long t_now = wall_clock64(); "
+               "atomicAdd(&P.prof[ph], t_now - t_prev); t_prev = t_now; }\n";
+    src += R"(// the pass's segments, one per tile from the first halo tile h0: seg_p[t] the
 // events of the bucket before segment t (only differences are used), seg_g[t] the
 // global index of its first event
 const int h0 = tb_h[a - A];
@@ -1144,8 +1175,9 @@ for (int t = sb + (int)threadIdx.x; t < se; t += SHB_TPB) {
     for (uint32_t j = (seg_p[t] - sbase + 31u) >> 5; j * 32u < x1; j++) seg_of[j] = (uint8_t)t;
 }
 __syncthreads();
-SHB_PROF(5)
-// global index of span event i (segments in span order)
+)";
+    src += phase(5);
+    src += R"(// global index of span event i (segments in span order)
 #define SHB_GIDX(i, out) { int sg_ = seg_of[(i) >> 5]; while (seg_p[sg_ + 1] - sbase <= (uint32_t)(i)) sg_++; \
     out = seg_g[sg_] + ((uint32_t)(i) - (seg_p[sg_] - sbase)); }
 if (threadIdx.x < 256) run[threadIdx.x] = 0u;
@@ -1167,8 +1199,9 @@ for (int k = 0; k < SHB_NR; k++) {
     src += R"(}
 for (int c = (int)threadIdx.x; c < (SHB_TPB / 64) * 256; c += SHB_TPB) (&wcnt[0][0])[c] = 0u;
 __syncthreads();
-SHB_PROF(0)
-// stable sort of the span by local key, staged in sorted order (the walks read
+)";
+    src += phase(0);
+    src += R"(// stable sort of the span by local key, staged in sorted order (the walks read
 // consecutive LDS words): each wave ranks its own events (kb ballots per round,
 // running per-key counts of the wave), one block pass combines the waves
 uint32_t rw[SHB_NR];
@@ -1233,8 +1266,8 @@ for (int k = 0; k < SHB_NR; k++) {
     for (int a : staged_out) src += "    " + lds(a) + "[pos] = vr" + std::to_string(a) + "[k];\n";
     src += R"(}
 __syncthreads();
-SHB_PROF(1)
 )";
+    src += phase(1);
     // slow_: some consumer took a partial beyond the mask's SHB_MSTEPS steps (its
     // match-stream values then come from a second walk)
     src += "int slow_ = 0;\n";
@@ -1256,9 +1289,8 @@ slow_ |= (int)(mask & SHB_MOVF);
 }
 __syncthreads();)";
     }
-    src += R"(
-SHB_PROF(2)
-// the counts to the events' slots; their exclusive prefix over the chunk
+    src += "\n" + phase(2);
+    src += R"(// the counts to the events' slots; their exclusive prefix over the chunk
 // (arrival order inside the bucket)
 uint32_t total;
 {
@@ -1297,8 +1329,8 @@ for (int t = ta + (int)threadIdx.x; t < se; t += SHB_TPB) {
     P.mstart[(int64_t)T * SHB_NB + b] = (uint32_t)rbase + q0;
     if (q1 > q0) atomicAdd(&P.ttot[T], q1 - q0);
 }
-SHB_PROF(3)
 )";
+    src += phase(3);
     // one 4-byte match-stream column (C2's e1.price): when no consumer needs the
     // slow walk (which reads s_ws), the values are staged in s_ws in region order
     // and the region goes out as one coalesced run
@@ -1348,7 +1380,7 @@ uint32_t k = 0;
            ms_put + "    }\n} else {\n" + walk(false, put) + "}\n";
     src += "}\n";
     if (stage1) src += "}\n";
-    src += "SHB_PROF(4)\na += ne;\n}\n}\n";
+    src += phase(4) + "a += ne;\n}\n}\n";
 
     return true;
 }
@@ -1511,5 +1543,10 @@ unsigned shj_tiles(int64_t n, uint32_t* tiles_per_xcd, uint32_t* ntiles) {
 }
 
 int shj_bucket_chunk(void) { return kChunk; }
+
+int shj_bucket_profiled(void) {
+    static const int prof = getenv("SH_BK_PROFILE") != nullptr;
+    return prof;
+}
 
 int shj_tile_size(void) { return kTile; }

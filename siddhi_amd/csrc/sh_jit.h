@@ -27,6 +27,9 @@ unsigned shj_tiles(int64_t n, uint32_t* tiles_per_xcd, uint32_t* ntiles);
 int shj_tile_size(void);
 // the bucketed matcher's consumer limit per pass (events; SH_BK_CH)
 int shj_bucket_chunk(void);
+// 1 when SH_BK_PROFILE asks for the bucketed matcher's phase clocks (read once per
+// process): the generator emits them and the host hands the kernel their buffer
+int shj_bucket_profiled(void);
 
 // bucketed window engine matcher (shb_match); ms_attrs: stream attributes the
 // match stream carries (e1-side select values), in match-stream column order
