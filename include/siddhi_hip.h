@@ -167,8 +167,9 @@ typedef struct sh_device_run {
     uint64_t* d_out_seq;         /* out: trigger_seq per match (ordered)            */
     int64_t* d_out_values;       /* out: out_capacity x n_out raw values            */
     int64_t out_count;           /* out: rows produced -- the count after an output-only
-                                    `having` (rows it drops are never written); a match
-                                    count above out_capacity before `having` is reported
+                                    `having` and `output first|last every N events` (rows
+                                    they drop are never written); a match count above
+                                    out_capacity before them is reported
                                     as a too-small out_capacity (SH_E_MORE, out_count the
                                     unfiltered count)                                  */
     void* stream;                /* hipStream_t to run on (NULL = default)          */

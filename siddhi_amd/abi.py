@@ -180,6 +180,12 @@ def bind_product(lib):
     lib.shx_having_rows.restype = C.c_int
     lib.shx_having_ms.argtypes = [C.c_void_p]
     lib.shx_having_ms.restype = C.c_double
+    lib.shx_rate_status.argtypes = [C.c_void_p]
+    lib.shx_rate_status.restype = C.c_int
+    lib.shx_rate_rows.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.shx_rate_rows.restype = C.c_int
+    lib.shx_rate_ms.argtypes = [C.c_void_p]
+    lib.shx_rate_ms.restype = C.c_double
     lib.shx_fingerprint.argtypes = [C.c_void_p]
     lib.shx_fingerprint.restype = C.c_uint64
     lib.shx_rules_status.argtypes = [C.c_void_p]

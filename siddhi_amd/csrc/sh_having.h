@@ -262,6 +262,20 @@ int shv_filter(const struct shv_prog* progs, int32_t n_progs, int64_t m, int32_t
                const int64_t* vals, const int32_t* query, const int64_t* ts, const uint8_t* nulls, uint64_t* o_seq,
                int64_t* o_vals, int32_t* o_query, int64_t* o_ts, uint8_t* o_nulls, uint32_t* ws,
                unsigned long long* d_kept, void* stream);
+// shv_filter with one more optional column: key[r] (the row's partition key) moves to
+// o_key with the kept rows
+int shv_filter_keyed(const struct shv_prog* progs, int32_t n_progs, int64_t m, int32_t n_out, const uint64_t* seq,
+                     const int64_t* vals, const int32_t* query, const int64_t* ts, const uint8_t* nulls,
+                     const int32_t* key, uint64_t* o_seq, int64_t* o_vals, int32_t* o_query, int64_t* o_ts,
+                     uint8_t* o_nulls, int32_t* o_key, uint32_t* ws, unsigned long long* d_kept, void* stream);
+// The same compaction from ready marks (the event limiter's, sh_rate.hip): mask holds
+// one 64-bit ballot word per 64 rows (whole tiles of SHV_TILE rows: rows past m are 0),
+// cnt the kept rows of every tile; off [tiles] and tmp [shd_scan_tmp_words(tiles)] are
+// scratch. The tiles' counts are scanned and the kept rows moved as shv_filter does.
+int shv_move_marked(int64_t m, int32_t n_out, const uint64_t* seq, const int64_t* vals, const int32_t* query,
+                    const int64_t* ts, const uint8_t* nulls, uint64_t* o_seq, int64_t* o_vals, int32_t* o_query,
+                    int64_t* o_ts, uint8_t* o_nulls, const uint64_t* mask, const uint32_t* cnt, uint32_t* off,
+                    uint32_t* tmp, unsigned long long* d_kept, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -389,49 +389,63 @@ static int lower_chain(sh_handle* h, const sh_app_desc* app, int qi, shp_program
     return SH_OK;
 }
 
-// order by / limit / offset / output rate limiting / group by, List outputs and a
-// `having` that reads a state-event attribute need the selector pass of the general
-// engine (2). A `having` over output attributes and constants alone is a predicate of
-// the finished row (sh_having.h): the fast engines take the app, with the device row
-// filter behind them (1: some query has one, its programs in *progs, one per query).
-// 0: none of these
-static int selector_extras(const sh_app_desc* app, std::vector<shv_prog>* progs) {
-    int having = 0;
+// order by / limit / offset / group by, List outputs, a `having` that reads a
+// state-event attribute and the limiters `output all every N events` / `output first
+// every T` need the selector pass of the general engine (SHX_GENERAL). A `having` over
+// output attributes and constants alone is a predicate of the finished row
+// (sh_having.h), and `output first|last every N events` a function of the row's ordinal
+// in its (query, key) (sh_rate.h): the fast engines take the app, with the device row
+// filter (SHX_HAVING: its programs in *progs, one per query) and the limiter pass
+// (SHX_RATE: its rules in *rules, one per query) behind them. 0: none of these
+enum { SHX_HAVING = 1, SHX_RATE = 2, SHX_GENERAL = 4 };
+static int selector_extras(const sh_app_desc* app, std::vector<shv_prog>* progs, std::vector<shl_rule>* rules) {
+    int extras = 0;
     if (progs) progs->assign((size_t)std::max(0, app->n_queries), shv_prog{});
+    if (rules) rules->assign((size_t)std::max(0, app->n_queries), shl_rule{SH_RATE_NONE, 0});
     for (int32_t q = 0; q < app->n_queries; q++) {
         const sh_query_desc& d = app->queries[q];
-        if (d.n_order > 0 || d.limit >= 0 || d.offset >= 0 || d.rate_kind != SH_RATE_NONE || d.n_group > 0) return 2;
+        if (d.n_order > 0 || d.limit >= 0 || d.offset >= 0 || d.n_group > 0) return SHX_GENERAL;
         // a List output (SH_OP_MULTI_VAR) is built by the general engine's selector
         for (int32_t o = 0; o < d.n_outputs; o++)
             if (d.outputs[o].expr >= 0 && d.outputs[o].expr < d.n_exprs && d.exprs[d.outputs[o].expr].op == SH_OP_MULTI_VAR)
-                return 2;
+                return SHX_GENERAL;
+        if (d.rate_kind != SH_RATE_NONE) {
+            // (`all every N` reorders: held rows leave with the N-th; `first every T`
+            // reads the playback clock per call)
+            if ((d.rate_kind != SH_RATE_FIRST_EVENTS && d.rate_kind != SH_RATE_LAST_EVENTS) || d.rate_value < 1 ||
+                getenv("SH_NO_RATE_FILTER"))
+                return SHX_GENERAL;
+            if (rules) (*rules)[q] = shl_rule{d.rate_kind, d.rate_value};
+            extras |= SHX_RATE;
+        }
         if (d.having >= 0) {
             shv_prog P;
-            if (getenv("SH_NO_HAVING_FILTER") || shv_lower(&d, &P)) return 2;
+            if (getenv("SH_NO_HAVING_FILTER") || shv_lower(&d, &P)) return SHX_GENERAL;
             if (progs) (*progs)[q] = P;
-            having = 1;
+            extras |= SHX_HAVING;
         }
     }
-    return having;
+    return extras;
 }
 
 static int compile_chain(sh_handle* h, const sh_app_desc* app) {
     if (app->n_queries != 1) return fail(h, SH_E_UNSUPPORTED, "chain engine: one query per app");
     std::vector<shv_prog> hv;
-    const int extras = selector_extras(app, &hv);
-    if (extras == 2)
-        return fail(h, SH_E_UNSUPPORTED, "chain engine: order by / limit / a having over state-event attributes run "
-                                         "on the general engine");
+    std::vector<shl_rule> rl;
+    const int extras = selector_extras(app, &hv, &rl);
+    if (extras & SHX_GENERAL)
+        return fail(h, SH_E_UNSUPPORTED, "chain engine: order by / limit / a having over state-event attributes / "
+                                         "time and all-events limiters run on the general engine");
     shp_program P;
     int rc = lower_chain(h, app, 0, P);
     if (rc) return rc;
-    // an output-only `having` on a window-shaped query: sh_push_batch stays on the
-    // general engine (whose selector applies it), sh_run_device takes the chain
-    // mode's rungs with the device row filter behind them (hv_chain, as has_rules
-    // does for a small rule set)
-    if (extras == 1 && !P.window_ok)
-        return fail(h, SH_E_UNSUPPORTED, "chain engine: having on a shape outside the window engines runs on the "
-                                         "general engine");
+    // an output-only `having` or an event limiter on a window-shaped query:
+    // sh_push_batch stays on the general engine (whose selector applies them),
+    // sh_run_device takes the chain mode's rungs with the device row filter and the
+    // limiter pass behind them (hv_chain, as has_rules does for a small rule set)
+    if (extras && !P.window_ok)
+        return fail(h, SH_E_UNSUPPORTED, "chain engine: having / output rate limiting on a shape outside the window "
+                                         "engines runs on the general engine");
     h->prog = P;
     h->n_out = P.n_out;
     h->partitioned = app->queries[0].partition >= 0;
@@ -441,10 +455,13 @@ static int compile_chain(sh_handle* h, const sh_app_desc* app) {
     // per-key state layout
     const char* capenv = getenv("SH_PARTIAL_CAP");
     set_layout(h->lay, P, capenv ? atoi(capenv) : 32);
-    if (extras == 1) {
-        h->hv_on = h->hv_chain = true;
+    if (extras) {
+        h->hv_chain = true;
+        h->hv_on = (extras & SHX_HAVING) != 0;
+        h->rl_on = (extras & SHX_RATE) != 0;
         h->hv_progs.swap(hv);
-        return fail(h, SH_E_UNSUPPORTED, "chain engine: having streams on the general engine");
+        h->rl_rules.swap(rl);
+        return fail(h, SH_E_UNSUPPORTED, "chain engine: having / output rate limiting stream on the general engine");
     }
     return SH_OK;
 }
@@ -470,10 +487,11 @@ static int compile_rules(sh_handle* h, const sh_app_desc* app) {
     if (app->n_queries < 2 || app->n_streams != 1)
         return fail(h, SH_E_UNSUPPORTED, "rule engine: two or more queries over one stream");
     std::vector<shv_prog> hv;
-    const int extras = selector_extras(app, &hv);
-    if (extras == 2)
-        return fail(h, SH_E_UNSUPPORTED,
-                    "rule engine: order by / limit / a having over state-event attributes run on the general engine");
+    std::vector<shl_rule> rl;
+    const int extras = selector_extras(app, &hv, &rl);
+    if (extras & SHX_GENERAL)
+        return fail(h, SH_E_UNSUPPORTED, "rule engine: order by / limit / a having over state-event attributes / time "
+                                         "and all-events limiters run on the general engine");
     const int part = app->queries[0].partition;
     std::vector<shr_rule> rules(app->n_queries);
     std::unique_ptr<sh_handle> tmp(new sh_handle());
@@ -572,8 +590,10 @@ static int compile_rules(sh_handle* h, const sh_app_desc* app) {
     h->r_rules.swap(rules);
     h->r_partitioned = part >= 0;
     h->has_rules = true;
-    h->hv_on = extras == 1;
+    h->hv_on = (extras & SHX_HAVING) != 0;
+    h->rl_on = (extras & SHX_RATE) != 0;
     h->hv_progs.swap(hv);
+    h->rl_rules.swap(rl);
     return SH_OK;
 }
 
@@ -756,6 +776,9 @@ static uint64_t program_fingerprint(const sh_handle* h) {
         // ... and every rule's `having` program (a set without one keeps its fingerprint)
         if (h->hv_on)
             for (const shv_prog& P : h->hv_progs) f = fnv1a(&P, sizeof(P), f);
+        // ... and every rule's event limiter (kind, N), likewise
+        if (h->rl_on)
+            for (const shl_rule& R : h->rl_rules) f = fnv1a(&R, sizeof(R), f);
         return f;
     }
     f = fnv1a(&h->prog, sizeof(h->prog), f);
@@ -789,7 +812,7 @@ int sh_compile(const sh_app_desc* app, sh_handle** out) {
         const bool rules = compile_rules(h, app) == SH_OK;
         const std::string rules_err = rules ? std::string() : h->err;
         rc = compile_nfa(h, app);
-        if (rc && h->hv_chain) h->hv_on = h->hv_chain = false;
+        if (rc && h->hv_chain) h->hv_on = h->rl_on = h->hv_chain = false;
         if (rc && rules) {
             // rule sets beyond the general engine's query table: bulk path only
             rc = SH_OK;
@@ -825,6 +848,11 @@ int sh_compile(const sh_app_desc* app, sh_handle** out) {
         if (h->hv_d_progs.ensure(h->hv_progs.size() * sizeof(shv_prog)) || h->hv_kept.ensure(64))
             return fail(h, SH_E_OOM, "hipMalloc failed");
         hipMemcpy(h->hv_d_progs.p, h->hv_progs.data(), h->hv_progs.size() * sizeof(shv_prog), hipMemcpyHostToDevice);
+    }
+    if (h->rl_on) {
+        if (h->rl_d_rules.ensure(h->rl_rules.size() * sizeof(shl_rule)) || h->rl_kept.ensure(64))
+            return fail(h, SH_E_OOM, "hipMalloc failed");
+        hipMemcpy(h->rl_d_rules.p, h->rl_rules.data(), h->rl_rules.size() * sizeof(shl_rule), hipMemcpyHostToDevice);
     }
     h->stores.resize(app->n_streams);
     for (int s = 0; s < app->n_streams; s++) {
@@ -905,7 +933,9 @@ void sh_destroy(sh_handle* h) {
         h->rc_ws.release();
         h->rc_oq.release();
         h->rc_ots.release();
-        DevBuf* hvb[] = {&h->hv_d_progs, &h->hv_ws, &h->hv_kept, &h->hv_seq, &h->hv_q, &h->hv_ts, &h->hv_vals};
+        DevBuf* hvb[] = {&h->hv_d_progs, &h->hv_ws, &h->hv_kept, &h->hv_seq, &h->hv_q, &h->hv_ts, &h->hv_vals, &h->hv_key,
+                         &h->rl_d_rules, &h->rl_ws, &h->rl_kept, &h->rl_seq, &h->rl_q, &h->rl_ts, &h->rl_vals,
+                         &h->rl_keys, &h->rl_state, &h->rl_ctl};
         for (DevBuf* b : hvb) b->release();
         for (auto& st : h->stores) {
             for (auto& c : st.cols) c.release();
@@ -916,6 +946,8 @@ void sh_destroy(sh_handle* h) {
         for (auto& e : h->bk_ev)
             if (e) hipEventDestroy(e);
         for (auto& e : h->hv_ev)
+            if (e) hipEventDestroy(e);
+        for (auto& e : h->rl_ev)
             if (e) hipEventDestroy(e);
         if (h->bk_side) hipStreamDestroy(h->bk_side);
         hipStreamDestroy(h->own_stream);
@@ -1617,13 +1649,16 @@ static int run_engines(sh_handle* h, sh_device_run* run, bool* general) {
     return run_chain(h, run, nkeys);
 }
 
-// Under an output-only `having` (h->hv_on) every rung writes raw rows, sequence
-// numbers and (for a rule set) query ids into the filter's source buffers; the
-// device row filter (sh_having.hip) then writes the kept rows where the caller's
-// rows go (its raw buffers, or the workspace the packed-row / typed-column
+// The row post-filter stage. Under an output-only `having` (h->hv_on) or an event
+// limiter (h->rl_on) every rung writes raw rows, sequence numbers and (for a rule set)
+// query ids into the stage's source buffers; `having` (sh_having.hip), then the
+// limiters (sh_rate.hip) on the rows it kept, then write the kept rows where the
+// caller's rows go (its raw buffers, or the workspace the packed-row / typed-column
 // conversion reads), once, after whichever rung produced the standing rows. None of
-// the rungs knows `having`; aggregators are updated by every match, kept or not.
-static int run_device_having(sh_handle* h, sh_device_run* run) {
+// the rungs knows either; aggregators are updated by every match, kept or not, and
+// every call starts every limiter's counter at zero, as the chain mode starts from
+// fresh per-key state.
+static int run_device_post(sh_handle* h, sh_device_run* run) {
     int rc = rows_for_cols(h, run);
     if (rc) return rc;
     const int no = std::max(1, h->n_out);
@@ -1631,11 +1666,14 @@ static int run_device_having(sh_handle* h, sh_device_run* run) {
     int64_t* dst_vals = run->d_out_values;
     uint64_t* dst_seq = run->d_out_seq;
     int32_t* dst_q = run->d_out_query;
-    const bool want_q = dst_q != nullptr || h->hv_progs.size() > 1;
+    const bool want_q = dst_q != nullptr || h->hv_progs.size() > 1 || h->rl_rules.size() > 1;
+    const bool both = h->hv_on && h->rl_on;
+    // the limiters key a partitioned app's rows by their trigger events: sequence numbers
+    const bool want_seq = dst_seq != nullptr || (h->rl_on && h->partitioned);
     if (!dst_vals) return fail(h, SH_E_INVALID_ARG, "sh_run_device: d_out_values is NULL");
     if (h->hv_vals.ensure_fresh(cap * no * 8) || h->hv_seq.ensure_fresh(cap * 8) ||
         (want_q && h->hv_q.ensure_fresh(cap * 4)))
-        return fail(h, SH_E_OOM, "having filter buffers");
+        return fail(h, SH_E_OOM, "row filter buffers");
     run->d_out_values = h->hv_vals.as<int64_t>();
     run->d_out_seq = h->hv_seq.as<uint64_t>();
     run->d_out_query = want_q ? h->hv_q.as<int32_t>() : nullptr;
@@ -1645,10 +1683,10 @@ static int run_device_having(sh_handle* h, sh_device_run* run) {
     run->d_out_seq = dst_seq;
     run->d_out_query = dst_q;
     if (rc != SH_OK) return rc;  // (a too-small out_capacity: the unfiltered count, as without `having`)
-    const int64_t m = run->out_count;
-    if (m < 0 || m > run->out_capacity) return fail(h, SH_E_HIP, "having filter: row count out of range");
+    int64_t m = run->out_count;
+    if (m < 0 || m > run->out_capacity) return fail(h, SH_E_HIP, "row filter: row count out of range");
     if (general) {
-        // the general engine's selector applied `having`: its rows as they are
+        // the general engine's selector applied `having` and the limiters: its rows as they are
         if (m > 0) {
             hipMemcpyAsync(dst_vals, h->hv_vals.p, (size_t)m * no * 8, hipMemcpyDeviceToDevice, h->stream);
             if (dst_seq) hipMemcpyAsync(dst_seq, h->hv_seq.p, (size_t)m * 8, hipMemcpyDeviceToDevice, h->stream);
@@ -1657,17 +1695,44 @@ static int run_device_having(sh_handle* h, sh_device_run* run) {
         }
         return SH_OK;
     }
-    rc = having_filter(h, m, no, h->hv_seq.as<uint64_t>(), h->hv_vals.as<int64_t>(),
-                       want_q ? h->hv_q.as<int32_t>() : nullptr, nullptr, dst_seq, dst_vals, dst_q, nullptr);
-    if (rc) return rc;
+    const uint64_t* src_seq = h->hv_seq.as<uint64_t>();
+    const int64_t* src_vals = h->hv_vals.as<int64_t>();
+    const int32_t* src_q = want_q ? h->hv_q.as<int32_t>() : nullptr;
     unsigned long long kept = 0;
-    hipMemcpyAsync(&kept, h->hv_kept.p, 8, hipMemcpyDeviceToHost, h->stream);
-    if (hipStreamSynchronize(h->stream) != hipSuccess || (int64_t)kept > m)
-        return fail(h, SH_E_HIP, "device error in the having filter");
+    if (h->hv_on) {
+        // (with limiters behind it: into their source buffers)
+        if (both && (h->rl_vals.ensure_fresh(cap * no * 8) || h->rl_seq.ensure_fresh(cap * 8) ||
+                     (want_q && h->rl_q.ensure_fresh(cap * 4))))
+            return fail(h, SH_E_OOM, "row filter buffers");
+        uint64_t* o_seq = both ? (want_seq ? h->rl_seq.as<uint64_t>() : nullptr) : dst_seq;
+        int64_t* o_vals = both ? h->rl_vals.as<int64_t>() : dst_vals;
+        int32_t* o_q = both ? (want_q ? h->rl_q.as<int32_t>() : nullptr) : dst_q;
+        rc = having_filter(h, m, no, src_seq, src_vals, src_q, nullptr, o_seq, o_vals, o_q, nullptr);
+        if (rc) return rc;
+        hipMemcpyAsync(&kept, h->hv_kept.p, 8, hipMemcpyDeviceToHost, h->stream);
+        if (hipStreamSynchronize(h->stream) != hipSuccess || (int64_t)kept > m)
+            return fail(h, SH_E_HIP, "device error in the having filter");
+        h->hv_last = 1;
+        h->hv_rows_in = m;
+        h->hv_rows_kept = (int64_t)kept;
+        m = (int64_t)kept;
+        src_seq = o_seq;
+        src_vals = o_vals;
+        src_q = o_q;
+    }
+    if (h->rl_on) {
+        const int32_t nkeys = h->partitioned ? std::max(1, run->n_keys) : 1;
+        rc = rate_limit(h, m, no, src_seq, src_vals, src_q, nullptr, nullptr, h->partitioned ? run->d_keys : nullptr,
+                        nkeys, nullptr, dst_seq, dst_vals, dst_q, nullptr, nullptr, nullptr);
+        if (rc) return rc;
+        hipMemcpyAsync(&kept, h->rl_kept.p, 8, hipMemcpyDeviceToHost, h->stream);
+        if (hipStreamSynchronize(h->stream) != hipSuccess || (int64_t)kept > m)
+            return fail(h, SH_E_HIP, "device error in the event limiters");
+        h->rl_last = 1;
+        h->rl_rows_in = m;
+        h->rl_rows_kept = (int64_t)kept;
+    }
     run->out_count = (int64_t)kept;
-    h->hv_last = 1;
-    h->hv_rows_in = m;
-    h->hv_rows_kept = (int64_t)kept;
     return SH_OK;
 }
 
@@ -1679,8 +1744,8 @@ static int run_device_impl(sh_handle* h, sh_device_run* run) {
     // were written there (the handle's own stream is non-blocking and would not
     // wait for them)
     h->stream = (hipStream_t)run->stream;
-    h->hv_last = 0;
-    if (h->hv_on) return run_device_having(h, run);
+    h->hv_last = h->rl_last = 0;
+    if (h->hv_on || h->rl_on) return run_device_post(h, run);
     bool general = false;
     return run_engines(h, run, &general);
 }
@@ -1849,6 +1914,24 @@ int shx_having_rows(sh_handle* h, int64_t* rows_in, int64_t* rows_kept) {
 double shx_having_ms(sh_handle* h) {
     float ms = 0.f;
     if (!h || !h->hv_last || !h->hv_ev[1] || hipEventElapsedTime(&ms, h->hv_ev[0], h->hv_ev[1]) != hipSuccess) return 0.0;
+    return ms;
+}
+
+// the event limiters of the last sh_run_device or streaming step: 1 the device pass
+// (sh_rate.hip) applied them, 0 there is none or the general engine's selector did
+int shx_rate_status(sh_handle* h) { return h ? h->rl_last : 0; }
+// ... and that pass's rows in and rows kept (0, 0 when it did not run)
+int shx_rate_rows(sh_handle* h, int64_t* rows_in, int64_t* rows_kept) {
+    if (!h) return 0;
+    if (rows_in) *rows_in = h->rl_last ? h->rl_rows_in : 0;
+    if (rows_kept) *rows_kept = h->rl_last ? h->rl_rows_kept : 0;
+    return h->rl_last;
+}
+
+// device time of the last run's or step's limiter launches (sorts, scan, move), ms
+double shx_rate_ms(sh_handle* h) {
+    float ms = 0.f;
+    if (!h || !h->rl_last || !h->rl_ev[1] || hipEventElapsedTime(&ms, h->rl_ev[0], h->rl_ev[1]) != hipSuccess) return 0.0;
     return ms;
 }
 

@@ -90,24 +90,26 @@ int agg_carry_cols(const sh_handle* h) {
     return D.n_cols;
 }
 
-shq_table agg_carry_table(const sh_handle* h) {
+shq_table carry_table(const CarryTab& C) {
     shq_table T;
     memset(&T, 0, sizeof(T));
-    T.keys = h->ag_keys.as<uint64_t>();
-    T.state = h->ag_state.as<int64_t>();
-    T.cap = h->ag_cap;
-    T.n_cols = h->ag_ncols;
+    T.keys = C.keys.as<uint64_t>();
+    T.state = C.state.as<int64_t>();
+    T.cap = C.cap;
+    T.n_cols = C.ncols;
     return T;
 }
 
+shq_table agg_carry_table(sh_handle* h) { return carry_table(agg_tab(h)); }
+
 // room for `add` more entries at no more than half full: the table is rebuilt at
 // (at least) double capacity, every entry kept -- the one place a step costs O(table)
-int agg_carry_reserve(sh_handle* h, int64_t add, int n_cols) {
+int carry_reserve(sh_handle* h, const CarryTab& C, int64_t add, int n_cols) {
     hipStream_t st = h->stream;
-    if (h->ag_ctl.ensure_fresh(64)) return SH_E_OOM;
-    const int64_t need = (h->ag_entries + add) * 2;
-    if (h->ag_cap > 0 && need <= h->ag_cap && h->ag_ncols == n_cols) return SH_OK;
-    int64_t cap = std::max<int64_t>(1024, h->ag_cap * 2);
+    if (C.ctl.ensure_fresh(64)) return SH_E_OOM;
+    const int64_t need = (C.entries + add) * 2;
+    if (C.cap > 0 && need <= C.cap && C.ncols == n_cols) return SH_OK;
+    int64_t cap = std::max<int64_t>(1024, C.cap * 2);
     while (cap < need) cap *= 2;
     DevBuf nk, nst;
     if (nk.ensure_fresh((size_t)cap * 8) || nst.ensure_fresh((size_t)cap * n_cols * 16)) {
@@ -116,44 +118,45 @@ int agg_carry_reserve(sh_handle* h, int64_t add, int n_cols) {
         return SH_E_OOM;
     }
     hipMemsetAsync(nk.p, 0xFF, (size_t)cap * 8, st);  // SHQ_EMPTY
-    hipMemsetAsync(h->ag_ctl.p, 0, 16, st);
+    hipMemsetAsync(C.ctl.p, 0, 16, st);
     int rc = 0;
-    if (h->ag_cap > 0 && h->ag_entries > 0) {
+    if (C.cap > 0 && C.entries > 0) {
         shq_table T;
         memset(&T, 0, sizeof(T));
         T.keys = nk.as<uint64_t>();
         T.state = nst.as<int64_t>();
         T.cap = cap;
         T.n_cols = n_cols;
-        rc = shc_put(&T, h->ag_keys.as<uint64_t>(), h->ag_state.as<int64_t>(), h->ag_cap,
-                     h->ag_ctl.as<unsigned long long>(), h->ag_ctl.as<int32_t>() + 2, st);
+        rc = shc_put(&T, C.keys.as<uint64_t>(), C.state.as<int64_t>(), C.cap, C.ctl.as<unsigned long long>(),
+                     C.ctl.as<int32_t>() + 2, st);
     }
     uint64_t ctl[2] = {0, 0};
-    hipMemcpyAsync(ctl, h->ag_ctl.p, 16, hipMemcpyDeviceToHost, st);
-    if (rc || hipStreamSynchronize(st) != hipSuccess || (ctl[1] & 1) || (int64_t)ctl[0] != h->ag_entries) {
+    hipMemcpyAsync(ctl, C.ctl.p, 16, hipMemcpyDeviceToHost, st);
+    if (rc || hipStreamSynchronize(st) != hipSuccess || (ctl[1] & 1) || (int64_t)ctl[0] != C.entries) {
         nk.release();
         nst.release();
         return SH_E_HIP;
     }
-    h->ag_keys.release();
-    h->ag_state.release();
-    h->ag_keys = nk;
-    h->ag_state = nst;
-    h->ag_cap = cap;
-    h->ag_ncols = n_cols;
+    C.keys.release();
+    C.state.release();
+    C.keys = nk;
+    C.state = nst;
+    C.cap = cap;
+    C.ncols = n_cols;
     return SH_OK;
 }
 
+int agg_carry_reserve(sh_handle* h, int64_t add, int n_cols) { return carry_reserve(h, agg_tab(h), add, n_cols); }
+
 // the table emptied and filled with n entries (restore; n = 0: a fresh handle's)
-int agg_carry_load(sh_handle* h, const uint64_t* keys, const int64_t* state, int64_t n) {
+int carry_load(sh_handle* h, const CarryTab& C, int nc, const uint64_t* keys, const int64_t* state, int64_t n) {
     hipStream_t st = h->stream;
-    const int nc = agg_carry_cols(h);
-    h->ag_entries = 0;
-    if (h->ag_cap > 0) hipMemsetAsync(h->ag_keys.p, 0xFF, (size_t)h->ag_cap * 8, st);
-    if (h->ag_ctl.p) hipMemsetAsync(h->ag_ctl.p, 0, 16, st);
+    C.entries = 0;
+    if (C.cap > 0) hipMemsetAsync(C.keys.p, 0xFF, (size_t)C.cap * 8, st);
+    if (C.ctl.p) hipMemsetAsync(C.ctl.p, 0, 16, st);
     if (n <= 0) return hipStreamSynchronize(st) == hipSuccess ? SH_OK : SH_E_HIP;
     if (nc < 1) return SH_E_INVALID_ARG;
-    if (agg_carry_reserve(h, n, nc)) return SH_E_OOM;
+    if (carry_reserve(h, C, n, nc)) return SH_E_OOM;
     DevBuf dk, ds;
     int rc = SH_OK;
     uint64_t ctl[2] = {0, 0};
@@ -162,32 +165,36 @@ int agg_carry_load(sh_handle* h, const uint64_t* keys, const int64_t* state, int
     } else {
         hipMemcpyAsync(dk.p, keys, (size_t)n * 8, hipMemcpyHostToDevice, st);
         hipMemcpyAsync(ds.p, state, (size_t)n * nc * 16, hipMemcpyHostToDevice, st);
-        hipMemsetAsync(h->ag_ctl.p, 0, 16, st);
-        const shq_table T = agg_carry_table(h);
-        if (shc_put(&T, dk.as<uint64_t>(), ds.as<int64_t>(), n, h->ag_ctl.as<unsigned long long>(),
-                    h->ag_ctl.as<int32_t>() + 2, st))
+        hipMemsetAsync(C.ctl.p, 0, 16, st);
+        const shq_table T = carry_table(C);
+        if (shc_put(&T, dk.as<uint64_t>(), ds.as<int64_t>(), n, C.ctl.as<unsigned long long>(),
+                    C.ctl.as<int32_t>() + 2, st))
             rc = SH_E_HIP;
-        hipMemcpyAsync(ctl, h->ag_ctl.p, 16, hipMemcpyDeviceToHost, st);
+        hipMemcpyAsync(ctl, C.ctl.p, 16, hipMemcpyDeviceToHost, st);
         if (hipStreamSynchronize(st) != hipSuccess || (ctl[1] & 1)) rc = SH_E_HIP;
     }
     dk.release();
     ds.release();
     if (rc) return rc;
     if ((int64_t)ctl[0] != n) return SH_E_INVALID_ARG;  // (a key twice)
-    h->ag_entries = n;
+    C.entries = n;
     return SH_OK;
 }
 
+int agg_carry_load(sh_handle* h, const uint64_t* keys, const int64_t* state, int64_t n) {
+    return carry_load(h, agg_tab(h), agg_carry_cols(h), keys, state, n);
+}
+
 // the live entries sorted by table key, each with its per-column state
-int agg_carry_dump(sh_handle* h, std::vector<uint64_t>& keys, std::vector<int64_t>& state) {
+int carry_dump(const CarryTab& C, std::vector<uint64_t>& keys, std::vector<int64_t>& state) {
     keys.clear();
     state.clear();
-    if (h->ag_cap <= 0 || h->ag_entries <= 0) return SH_OK;
-    const size_t cap = (size_t)h->ag_cap, w = (size_t)h->ag_ncols * 2;
+    if (C.cap <= 0 || C.entries <= 0) return SH_OK;
+    const size_t cap = (size_t)C.cap, w = (size_t)C.ncols * 2;
     std::vector<uint64_t> k(cap);
     std::vector<int64_t> s(cap * w);
-    if (hipMemcpy(k.data(), h->ag_keys.p, cap * 8, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(s.data(), h->ag_state.p, cap * w * 8, hipMemcpyDeviceToHost) != hipSuccess)
+    if (hipMemcpy(k.data(), C.keys.p, cap * 8, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(s.data(), C.state.p, cap * w * 8, hipMemcpyDeviceToHost) != hipSuccess)
         return SH_E_HIP;
     std::vector<size_t> live;
     for (size_t i = 0; i < cap; i++)
@@ -197,7 +204,11 @@ int agg_carry_dump(sh_handle* h, std::vector<uint64_t>& keys, std::vector<int64_
         keys.push_back(k[i]);
         state.insert(state.end(), s.begin() + i * w, s.begin() + (i + 1) * w);
     }
-    return (int64_t)keys.size() == h->ag_entries ? SH_OK : SH_E_HIP;
+    return (int64_t)keys.size() == C.entries ? SH_OK : SH_E_HIP;
+}
+
+int agg_carry_dump(sh_handle* h, std::vector<uint64_t>& keys, std::vector<int64_t>& state) {
+    return carry_dump(agg_tab(h), keys, state);
 }
 
 // sh_run_device on a rule set beyond the general engine's table whose additions
@@ -655,17 +666,35 @@ int rules_stage(sh_handle* h, const sh_batch* b) {
 // the device row filter (sh_having.hip) over m ordered raw rows, launched on the
 // handle's stream: the kept rows go to the o_* buffers, their count to h->hv_kept
 int having_filter(sh_handle* h, int64_t m, int n_out, const uint64_t* seq, const int64_t* vals, const int32_t* query,
-                  const int64_t* ts, uint64_t* o_seq, int64_t* o_vals, int32_t* o_query, int64_t* o_ts) {
+                  const int64_t* ts, uint64_t* o_seq, int64_t* o_vals, int32_t* o_query, int64_t* o_ts,
+                  const int32_t* key, int32_t* o_key) {
     if (h->hv_ws.ensure_fresh((size_t)shv_filter_ws_words(m) * 4) || h->hv_kept.ensure(64))
         return fail(h, SH_E_OOM, "having filter workspace");
     for (auto& e : h->hv_ev)
         if (!e) hipEventCreate(&e);
     hipEventRecord(h->hv_ev[0], h->stream);
-    if (shv_filter(h->hv_d_progs.as<shv_prog>(), (int32_t)h->hv_progs.size(), m, n_out, seq, vals, query, ts, nullptr,
-                   o_seq, o_vals, o_query, o_ts, nullptr, h->hv_ws.as<uint32_t>(),
-                   h->hv_kept.as<unsigned long long>(), h->stream))
+    if (shv_filter_keyed(h->hv_d_progs.as<shv_prog>(), (int32_t)h->hv_progs.size(), m, n_out, seq, vals, query, ts,
+                         nullptr, key, o_seq, o_vals, o_query, o_ts, nullptr, o_key, h->hv_ws.as<uint32_t>(),
+                         h->hv_kept.as<unsigned long long>(), h->stream))
         return fail(h, SH_E_HIP, "having filter launch failed");
     hipEventRecord(h->hv_ev[1], h->stream);
+    return SH_OK;
+}
+
+int rate_limit(sh_handle* h, int64_t m, int n_out, const uint64_t* seq, const int64_t* vals, const int32_t* query,
+               const int64_t* ts, const int32_t* rowkey, const int32_t* keys, int32_t n_keys, const shq_table* T,
+               uint64_t* o_seq, int64_t* o_vals, int32_t* o_query, int64_t* o_ts, const uint64_t** put_keys,
+               const int64_t** put_state) {
+    if (h->rl_ws.ensure_fresh((size_t)shl_limit_ws_words(m) * 4) || h->rl_kept.ensure(64))
+        return fail(h, SH_E_OOM, "event limiter workspace");
+    for (auto& e : h->rl_ev)
+        if (!e) hipEventCreate(&e);
+    hipEventRecord(h->rl_ev[0], h->stream);
+    if (shl_limit(h->rl_d_rules.as<shl_rule>(), (int32_t)h->rl_rules.size(), m, n_out, seq, vals, query, ts, nullptr,
+                  rowkey, keys, n_keys, 0, T, o_seq, o_vals, o_query, o_ts, nullptr, h->rl_ws.as<uint32_t>(),
+                  h->rl_kept.as<unsigned long long>(), h->stream, put_keys, put_state))
+        return fail(h, SH_E_HIP, "event limiter launch failed");
+    hipEventRecord(h->rl_ev[1], h->stream);
     return SH_OK;
 }
 
@@ -801,6 +830,8 @@ int rules_step(sh_handle* h) {
     int32_t flag = 0;
     const uint64_t* ag_pk = nullptr;   // carried aggregates: the step's segment heads and
     const int64_t* ag_fin = nullptr;   // their final states (shc_running)
+    const uint64_t* rl_pk = nullptr;   // event limiters: the step's runs and their next
+    const int64_t* rl_fin = nullptr;   // counters (shl_limit)
     hipMemcpyAsync(&lo, off + (n - 1), 4, hipMemcpyDeviceToHost, st);
     hipMemcpyAsync(&lc, cnt + (n - 1), 4, hipMemcpyDeviceToHost, st);
     hipMemcpyAsync(&npairs, soff + n, 4, hipMemcpyDeviceToHost, st);
@@ -809,7 +840,8 @@ int rules_step(sh_handle* h) {
     if (hipStreamSynchronize(st) != hipSuccess) return rules_step_fail(h, SH_E_HIP, "device error in the rule scan");
     if (flag) return rules_step_fail(h, SH_E_UNSUPPORTED, "rule engine: timestamps decrease inside a key");
     const int64_t m = (int64_t)lo + lc;
-    int64_t mk = m;  // the rows that reach the host queue (after `having`)
+    int64_t mk = m;   // the rows that reach the host queue (after `having` and the event limiters)
+    int64_t ml = 0;   // ... that reached the limiters (after `having`)
     // the next carried state, beside the current one
     oom = Bn.ts.ensure_fresh(std::max<size_t>(nrows, 1) * 8) | Bn.key.ensure_fresh(std::max<size_t>(nrows, 1) * 4) |
           Bn.seq.ensure_fresh(std::max<size_t>(nrows, 1) * 8) | Bn.c_off.ensure_fresh(((size_t)nrows + 1) * 4) |
@@ -832,6 +864,7 @@ int rules_step(sh_handle* h) {
         shr_write(dT, sts, skeys, n, sentinel, dC, cnt, off, rec_p, rec_q, rec_r, st, img, &h->r_img, nullptr, 0, &K))
         return rules_step_fail(h, SH_E_HIP, "rule write launch failed");
     const int no = std::max(1, h->n_out);
+    const bool rl_keyed = h->rl_on && sorted;  // the limiters' runs are per (query, partition key)
     if (m > 0) {
         if (h->w_oseq.ensure_fresh((size_t)m * 8) || h->rc_ots.ensure_fresh((size_t)m * 8) ||
             h->rc_oq.ensure_fresh((size_t)m * 4) || h->w_ovals.ensure_fresh((size_t)m * no * 8))
@@ -849,6 +882,12 @@ int rules_step(sh_handle* h) {
             if ((sorted && h->rc_okey.ensure_fresh((size_t)m * 4)) ||
                 h->a_scratch.ensure_fresh((size_t)shc_scratch_bytes(m, AD.n_cols)) || agg_carry_reserve(h, m, AD.n_cols))
                 return rules_step_fail(h, SH_E_OOM, "carried aggregates");
+            h->step_okey = sorted ? h->rc_okey.as<int32_t>() : nullptr;
+        }
+        if (h->rl_on) {
+            // the limiters' counters: keyed and reserved as the aggregates' states are
+            if ((sorted && h->rc_okey.ensure_fresh((size_t)m * 4)) || carry_reserve(h, rate_tab(h), m, 1))
+                return rules_step_fail(h, SH_E_OOM, "carried limiter counters");
             h->step_okey = sorted ? h->rc_okey.as<int32_t>() : nullptr;
         }
         h->step_seqs = A.seq.as<uint64_t>();
@@ -872,16 +911,41 @@ int rules_step(sh_handle* h) {
         // filter's own buffers (the aggregate table below takes every row's state)
         if (h->hv_on) {
             if (h->hv_seq.ensure_fresh((size_t)m * 8) || h->hv_ts.ensure_fresh((size_t)m * 8) ||
-                h->hv_q.ensure_fresh((size_t)m * 4) || h->hv_vals.ensure_fresh((size_t)m * no * 8))
+                h->hv_q.ensure_fresh((size_t)m * 4) || h->hv_vals.ensure_fresh((size_t)m * no * 8) ||
+                (rl_keyed && h->hv_key.ensure_fresh((size_t)m * 4)))
                 return rules_step_fail(h, SH_E_OOM, "having filter buffers");
+            // (the limiters behind it key the kept rows: their keys move with them)
             if (having_filter(h, m, no, h->w_oseq.as<uint64_t>(), h->w_ovals.as<int64_t>(), h->rc_oq.as<int32_t>(),
                               h->rc_ots.as<int64_t>(), h->hv_seq.as<uint64_t>(), h->hv_vals.as<int64_t>(),
-                              h->hv_q.as<int32_t>(), h->hv_ts.as<int64_t>()))
+                              h->hv_q.as<int32_t>(), h->hv_ts.as<int64_t>(),
+                              rl_keyed ? h->rc_okey.as<int32_t>() : nullptr, rl_keyed ? h->hv_key.as<int32_t>() : nullptr))
                 return rules_step_fail(h, SH_E_HIP, h->err.c_str());
             unsigned long long kept = 0;
             hipMemcpyAsync(&kept, h->hv_kept.p, 8, hipMemcpyDeviceToHost, st);
             if (hipStreamSynchronize(st) != hipSuccess || (int64_t)kept > m)
                 return rules_step_fail(h, SH_E_HIP, "device error in the having filter");
+            mk = (int64_t)kept;
+        }
+        // the event limiters, on the rows `having` kept, from each run's carried counter
+        // (the counters' table moves last, below)
+        ml = mk;
+        if (h->rl_on && ml > 0) {
+            if (h->rl_seq.ensure_fresh((size_t)ml * 8) || h->rl_ts.ensure_fresh((size_t)ml * 8) ||
+                h->rl_q.ensure_fresh((size_t)ml * 4) || h->rl_vals.ensure_fresh((size_t)ml * no * 8))
+                return rules_step_fail(h, SH_E_OOM, "event limiter buffers");
+            const bool hv = h->hv_on;
+            const shq_table T = carry_table(rate_tab(h));
+            if (rate_limit(h, ml, no, (hv ? h->hv_seq : h->w_oseq).as<uint64_t>(),
+                           (hv ? h->hv_vals : h->w_ovals).as<int64_t>(), (hv ? h->hv_q : h->rc_oq).as<int32_t>(),
+                           (hv ? h->hv_ts : h->rc_ots).as<int64_t>(),
+                           rl_keyed ? (hv ? h->hv_key : h->rc_okey).as<int32_t>() : nullptr, nullptr, nkeys, &T,
+                           h->rl_seq.as<uint64_t>(), h->rl_vals.as<int64_t>(), h->rl_q.as<int32_t>(),
+                           h->rl_ts.as<int64_t>(), &rl_pk, &rl_fin))
+                return rules_step_fail(h, SH_E_HIP, h->err.c_str());
+            unsigned long long kept = 0;
+            hipMemcpyAsync(&kept, h->rl_kept.p, 8, hipMemcpyDeviceToHost, st);
+            if (hipStreamSynchronize(st) != hipSuccess || (int64_t)kept > ml)
+                return rules_step_fail(h, SH_E_HIP, "device error in the event limiters");
             mk = (int64_t)kept;
         }
     } else {
@@ -900,10 +964,10 @@ int rules_step(sh_handle* h) {
     h->o_vals.resize((base + mk) * h->n_out);
     h->o_nulls.resize((base + mk) * h->n_out, 0);
     if (mk > 0) {
-        const DevBuf& oq = h->hv_on ? h->hv_q : h->rc_oq;
-        const DevBuf& oseq = h->hv_on ? h->hv_seq : h->w_oseq;
-        const DevBuf& ots = h->hv_on ? h->hv_ts : h->rc_ots;
-        const DevBuf& ovals = h->hv_on ? h->hv_vals : h->w_ovals;
+        const DevBuf& oq = h->rl_on ? h->rl_q : h->hv_on ? h->hv_q : h->rc_oq;
+        const DevBuf& oseq = h->rl_on ? h->rl_seq : h->hv_on ? h->hv_seq : h->w_oseq;
+        const DevBuf& ots = h->rl_on ? h->rl_ts : h->hv_on ? h->hv_ts : h->rc_ots;
+        const DevBuf& ovals = h->rl_on ? h->rl_vals : h->hv_on ? h->hv_vals : h->w_ovals;
         hipMemcpyAsync(h->o_query.data() + base, oq.p, (size_t)mk * 4, hipMemcpyDeviceToHost, st);
         hipMemcpyAsync(h->o_seq.data() + base, oseq.p, (size_t)mk * 8, hipMemcpyDeviceToHost, st);
         hipMemcpyAsync(h->o_ts.data() + base, ots.p, (size_t)mk * 8, hipMemcpyDeviceToHost, st);
@@ -921,8 +985,17 @@ int rules_step(sh_handle* h) {
         arc = shc_put(&T, ag_pk, ag_fin, m, h->ag_ctl.as<unsigned long long>(), h->ag_ctl.as<int32_t>() + 2, st);
         hipMemcpyAsync(ag_ctl, h->ag_ctl.p, 16, hipMemcpyDeviceToHost, st);
     }
+    // ... and the limiters' next counters into theirs
+    uint64_t rl_ctl[2] = {0, 0};
+    if (rl_pk && !arc) {
+        const shq_table T = carry_table(rate_tab(h));
+        hipMemsetAsync(h->rl_ctl.p, 0, 16, st);
+        arc = shc_put(&T, rl_pk, rl_fin, ml, h->rl_ctl.as<unsigned long long>(), h->rl_ctl.as<int32_t>() + 2, st);
+        hipMemcpyAsync(rl_ctl, h->rl_ctl.p, 16, hipMemcpyDeviceToHost, st);
+    }
     if (shr_klast_update(sts, skeys, perm, n, (uint32_t)nc, h->rc_klast.as<int64_t>(), st) || arc ||
-        (hipEventRecord(h->ev[3], st), hipStreamSynchronize(st)) != hipSuccess || (ag_ctl[1] & 1)) {
+        (hipEventRecord(h->ev[3], st), hipStreamSynchronize(st)) != hipSuccess || (ag_ctl[1] & 1) ||
+        (rl_ctl[1] & 1)) {
         h->o_query.resize(base);
         h->o_seq.resize(base);
         h->o_ts.resize(base);
@@ -940,7 +1013,11 @@ int rules_step(sh_handle* h) {
     if (h->r_aggp) h->agg_last = 6;
     h->hv_last = h->hv_on ? 1 : 0;
     h->hv_rows_in = m;
-    h->hv_rows_kept = mk;
+    h->hv_rows_kept = ml;
+    if (rl_pk) h->rl_entries += (int64_t)rl_ctl[0];
+    h->rl_last = h->rl_on ? 1 : 0;
+    h->rl_rows_in = ml;
+    h->rl_rows_kept = mk;
     h->rq_ts.clear();
     h->rq_key.clear();
     h->rq_seq.clear();

@@ -30,6 +30,7 @@
 #include "sh_jit.h"
 #include "sh_jmap.h"
 #include "sh_nfa.h"
+#include "sh_rate.h"
 #include "sh_nfa_dev.h"
 #include "sh_nfa_lower.h"
 #include "sh_rules.h"
@@ -387,12 +388,28 @@ struct sh_handle {
     // copy, the filter's workspace and its destination buffers (a streaming step
     // hands the host queue the kept rows from them), and the last run's counts
     bool hv_on = false;
-    bool hv_chain = false;             // a one-query window-shaped app: mode 1 to stream, the chain rungs in bulk
+    bool hv_chain = false;             // a one-query window-shaped app (with a `having` or an event limiter):
+                                       // mode 1 to stream, the chain rungs in bulk
     std::vector<shv_prog> hv_progs;
-    DevBuf hv_d_progs, hv_ws, hv_kept, hv_seq, hv_q, hv_ts, hv_vals;
+    DevBuf hv_d_progs, hv_ws, hv_kept, hv_seq, hv_q, hv_ts, hv_vals, hv_key;
     int hv_last = 0;                   // 1: the device row filter ran in the last run or step
     int64_t hv_rows_in = 0, hv_rows_kept = 0;
     hipEvent_t hv_ev[2] = {};          // around the filter's launches (made by the first one)
+    // ---- `output first|last every N events` behind the fast engines (sh_rate.h /
+    // sh_rate.hip): one rule per query (SH_RATE_NONE keeps every row), the device copy,
+    // the pass's workspace and its destination buffers (as the filter's above), the
+    // last run's counts, and -- for a streaming rule set -- the carried counter of
+    // every (query, key) that ever reached a limiter, in a one-column table of the
+    // aggregates' kind (state[slot * 2]: the reduced counter of sh_rate.h)
+    bool rl_on = false;
+    std::vector<shl_rule> rl_rules;
+    DevBuf rl_d_rules, rl_ws, rl_kept, rl_seq, rl_q, rl_ts, rl_vals;
+    int rl_last = 0;                   // 1: the device pass ran in the last run or step
+    int64_t rl_rows_in = 0, rl_rows_kept = 0;
+    hipEvent_t rl_ev[2] = {};
+    DevBuf rl_keys, rl_state, rl_ctl;
+    int64_t rl_cap = 0, rl_entries = 0;
+    int32_t rl_ncols = 0;
     std::vector<int32_t> out_types;  // per select position over the queries (-2: types differ)
     uint64_t fp = 0;                 // compiled-program fingerprint (snapshot images)
 };
@@ -458,6 +475,18 @@ int nf_upload_table(sh_handle* h);
 int agg_post(sh_handle* h, sh_device_run* run, int32_t nkeys, const int32_t* d_query, int n_query,
              const int32_t* agg_kind, const int32_t* arg_type, int n_out);
 int agg_carry_cols(const sh_handle* h);
+// a carried-state table of the handle (the aggregates' or the limiters' counters)
+struct CarryTab {
+    DevBuf &keys, &state, &ctl;
+    int64_t &cap, &entries;
+    int32_t& ncols;
+};
+inline CarryTab agg_tab(sh_handle* h) { return {h->ag_keys, h->ag_state, h->ag_ctl, h->ag_cap, h->ag_entries, h->ag_ncols}; }
+inline CarryTab rate_tab(sh_handle* h) { return {h->rl_keys, h->rl_state, h->rl_ctl, h->rl_cap, h->rl_entries, h->rl_ncols}; }
+shq_table carry_table(const CarryTab& C);
+int carry_reserve(sh_handle* h, const CarryTab& C, int64_t add, int n_cols);
+int carry_dump(const CarryTab& C, std::vector<uint64_t>& keys, std::vector<int64_t>& state);
+int carry_load(sh_handle* h, const CarryTab& C, int n_cols, const uint64_t* keys, const int64_t* state, int64_t n);
 int agg_carry_dump(sh_handle* h, std::vector<uint64_t>& keys, std::vector<int64_t>& state);
 int agg_carry_load(sh_handle* h, const uint64_t* keys, const int64_t* state, int64_t n);
 int bits_for(uint64_t v);
@@ -484,7 +513,16 @@ int rules_step(sh_handle* h);
 // the device row filter over m ordered rows (sources and destinations apart, query /
 // ts NULL where the path has none); the kept count lands in h->hv_kept (8 bytes)
 int having_filter(sh_handle* h, int64_t m, int n_out, const uint64_t* seq, const int64_t* vals, const int32_t* query,
-                  const int64_t* ts, uint64_t* o_seq, int64_t* o_vals, int32_t* o_query, int64_t* o_ts);
+                  const int64_t* ts, uint64_t* o_seq, int64_t* o_vals, int32_t* o_query, int64_t* o_ts,
+                  const int32_t* key = nullptr, int32_t* o_key = nullptr);
+// the event limiters' pass (sh_rate.hip) over m ordered rows, as having_filter: keys
+// from rowkey, else keys[seq] (NULL, NULL: one key); T the carried counters (NULL:
+// every run from zero); the kept count lands in h->rl_kept, put_keys / put_state
+// take what shc_put carries
+int rate_limit(sh_handle* h, int64_t m, int n_out, const uint64_t* seq, const int64_t* vals, const int32_t* query,
+               const int64_t* ts, const int32_t* rowkey, const int32_t* keys, int32_t n_keys, const shq_table* T,
+               uint64_t* o_seq, int64_t* o_vals, int32_t* o_query, int64_t* o_ts, const uint64_t** put_keys,
+               const int64_t** put_state);
 int run_s3b(sh_handle* h, sh_device_run* run, int32_t nkeys);
 shd_segment_ws seg_ws(sh_handle* h, int64_t n);
 int tile_shift_for(int64_t n, int32_t nkeys);
@@ -499,6 +537,9 @@ int shx_agg_status(sh_handle* h);
 int shx_having_status(sh_handle* h);
 int shx_having_rows(sh_handle* h, int64_t* rows_in, int64_t* rows_kept);
 double shx_having_ms(sh_handle* h);
+int shx_rate_status(sh_handle* h);
+int shx_rate_rows(sh_handle* h, int64_t* rows_in, int64_t* rows_kept);
+double shx_rate_ms(sh_handle* h);
 uint64_t shx_fingerprint(sh_handle* h);
 int shx_rules_status(sh_handle* h);
 int shx_rules_carry(sh_handle* h, int64_t* partials, int64_t* rows);

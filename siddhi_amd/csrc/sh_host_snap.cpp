@@ -213,6 +213,16 @@ static int snapshot_image(sh_handle* h, SnapW& w) {
             w.vec(ak);
             w.vec(as);
         }
+        if (h->rl_on) {
+            // event limiters: the (query, key) runs sorted by table key, each with its counter
+            std::vector<uint64_t> lk;
+            std::vector<int64_t> ls;
+            if (carry_dump(rate_tab(h), lk, ls)) w.bad = true;
+            std::vector<uint32_t> lc(lk.size());
+            for (size_t i = 0; i < lk.size(); i++) lc[i] = (uint32_t)ls[i * 2];
+            w.vec(lk);
+            w.vec(lc);
+        }
     } else if (h->mode == 0) {
         w.put(h->lay);
         w.put(h->nkeys_alloc);
@@ -374,6 +384,23 @@ static int restore_image(sh_handle* h, const void* buf, int64_t size) {
             for (size_t i = 0; i < ak.size() && !r.bad; i++)
                 if (ak[i] == SHQ_EMPTY || (i && ak[i] <= ak[i - 1])) r.bad = true;
             if (!r.bad && agg_carry_load(h, ak.data(), as.data(), (int64_t)ak.size())) r.bad = true;
+        }
+        if (!r.bad && h->rl_on) {
+            std::vector<uint64_t> lk;
+            std::vector<uint32_t> lc;
+            r.vec(lk);
+            r.vec(lc);
+            if (lc.size() != lk.size()) r.bad = true;
+            for (size_t i = 0; i < lk.size() && !r.bad; i++) {
+                // ascending keys of limited queries, counters a limiter can hold
+                const uint64_t q = lk[i] >> 32;
+                if (lk[i] == SHQ_EMPTY || (i && lk[i] <= lk[i - 1]) || q >= h->rl_rules.size() ||
+                    !shl_limits(h->rl_rules[q]) || lc[i] >= (uint32_t)std::max(2, h->rl_rules[q].n))
+                    r.bad = true;
+            }
+            std::vector<int64_t> ls(lk.size() * 2, 0);
+            for (size_t i = 0; i < lk.size(); i++) ls[i * 2] = (int64_t)lc[i];
+            if (!r.bad && carry_load(h, rate_tab(h), 1, lk.data(), ls.data(), (int64_t)lk.size())) r.bad = true;
         }
         if (r.bad) h->rc_rows = h->rc_pairs = h->rc_nkeys = 0;
     } else if (h->mode == 0 && !r.bad) {

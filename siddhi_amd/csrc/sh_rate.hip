@@ -1,0 +1,342 @@
+// sh_rate.hip — `output first|last every N events` behind the fast engines: the keep
+// rule of sh_rate.h applied to the ordered raw rows an engine produced (after
+// `having`), as a segmented rank followed by a stable compaction.
+//
+//   k_shl_prep    one lane per row: the row's index and its sort key, query << kbits |
+//                 partition key in one 32-bit word when the key bits and the query bits
+//                 in use fit one
+//   (sort)        one stable LSD radix sort of (sort key, index) over the bits in use
+//                 (shd_sort_pairs): the rows of a (query, key) run become contiguous and
+//                 keep their output order, and the sorted words are the run keys
+//   (wide keys)   more than 32 bits in use: key and query apart, a sort by key, then by
+//                 query (k_shl_pick between them) and k_shl_gather, the 64-bit run key
+//                 query << 32 | key in sorted order
+//   k_shl_tile    tiles of SHL_TILE rows, 8 per lane in registers: a run's head (its
+//                 key differs from its predecessor's) looks its carried counter up and
+//                 forms head_position << 32 | counter, every other row 0; an inclusive
+//                 max-scan (DPP row shifts and broadcasts, one LDS word per wave)
+//                 gives every row the pair of the latest head inside the tile
+//   k_shl_carry   one workgroup: exclusive max-scan of the tiles' aggregates
+//   k_shl_out     ordinal = position - head + 1, shl_keep on it: one keep byte per row,
+//                 in row order; a run's last row writes (run key, next counter) for
+//                 shc_put (when the caller carries counters)
+//   k_shl_mark    64-bit ballots of the keep bytes and one kept count per tile of
+//                 SHV_TILE rows, then shv_move_marked (sh_having.hip): scan and move
+//
+// The pair of a head at position 0 with counter 0 is the scan's identity, which is
+// what a row before any head of its tile has until the carry reaches it.
+#include <hip/hip_runtime.h>
+#include <string.h>
+
+#include "sh_agg_seq.h"
+#include "sh_device.h"
+#include "sh_having.h"
+#include "sh_rate.h"
+#include "sh_wave.h"
+
+#define SHL_TPB 256
+#define SHL_ITEMS 8
+#define SHL_CARRY_TPB 1024
+static_assert(SHL_TPB * SHL_ITEMS == SHL_TILE, "tile = lanes x rows per lane");
+
+__device__ __forceinline__ uint64_t shl_max(uint64_t a, uint64_t b) { return a > b ? a : b; }
+
+// inclusive max-scan over the 64 lanes of a wave (sh_wave.h's scan with max in place
+// of the addition; a lane without a source reads 0, the identity)
+__device__ __forceinline__ uint64_t shl_wave_scan(uint64_t v) {
+    const int lane = threadIdx.x & 63, rl = lane & 15;
+    uint64_t t;
+    t = shw_move64<SHW_ROW_SHR(1)>(v);
+    if (rl >= 1) v = shl_max(v, t);
+    t = shw_move64<SHW_ROW_SHR(2)>(v);
+    if (rl >= 2) v = shl_max(v, t);
+    t = shw_move64<SHW_ROW_SHR(4)>(v);
+    if (rl >= 4) v = shl_max(v, t);
+    t = shw_move64<SHW_ROW_SHR(8)>(v);
+    if (rl >= 8) v = shl_max(v, t);
+    t = shw_move64<SHW_ROW_BCAST15>(v);
+    if ((lane & 31) >= 16) v = shl_max(v, t);
+    t = shw_move64<SHW_ROW_BCAST31>(v);
+    if (lane >= 32) v = shl_max(v, t);
+    return v;
+}
+
+// workgroup max-scan of one value per thread: *inc the inclusive value, the return
+// value the exclusive one (0 for thread 0); wsum: one word per wave
+template <int NT>
+__device__ __forceinline__ uint64_t shl_block_scan(uint64_t x, uint64_t* wsum, uint64_t* inc) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const uint64_t wi = shl_wave_scan(x);
+    if (lane == 63) wsum[w] = wi;
+    __syncthreads();
+    uint64_t pre = 0;
+    for (int i = 0; i < w; i++) pre = shl_max(pre, wsum[i]);
+    uint64_t up = (uint64_t)__shfl_up((long long)wi, 1, 64);
+    if (lane == 0) up = 0;
+    __syncthreads();
+    *inc = shl_max(pre, wi);
+    return shl_max(pre, up);
+}
+
+__global__ void __launch_bounds__(SHL_TPB) k_shl_prep(const uint64_t* __restrict__ seq, int64_t m,
+                                                      const int32_t* __restrict__ query,
+                                                      const int32_t* __restrict__ rowkey,
+                                                      const int32_t* __restrict__ keys, uint64_t seq_base,
+                                                      int kbits, uint32_t* __restrict__ klo,
+                                                      uint32_t* __restrict__ khi, uint32_t* __restrict__ idx) {
+    const int64_t r = (int64_t)blockIdx.x * SHL_TPB + threadIdx.x;
+    if (r >= m) return;
+    const uint32_t k = rowkey ? (uint32_t)rowkey[r] : keys ? (uint32_t)keys[seq[r] - seq_base] : 0u;
+    const uint32_t q = query ? (uint32_t)query[r] : 0u;
+    idx[r] = (uint32_t)r;
+    if (khi) {  // wide keys: apart
+        klo[r] = k;
+        khi[r] = q;
+    } else {
+        klo[r] = (q << kbits) | (k & ((1u << kbits) - 1u));
+    }
+}
+
+// the run key query << 32 | key of sorted position p: from the 64-bit keys (wide), else
+// from the sorted 32-bit word query << kbits | key (kbits < 32)
+__device__ __forceinline__ uint64_t shl_run_key(const uint32_t* __restrict__ s32, const uint64_t* __restrict__ s64,
+                                                int kbits, int64_t p) {
+    if (s64) return s64[p];
+    const uint32_t c = s32[p];
+    return shq_key((int32_t)(c >> kbits), (int32_t)(c & ((1u << kbits) - 1u)));
+}
+
+// (order and gv may be one array: a lane reads its entry before it writes it)
+__global__ void __launch_bounds__(SHL_TPB) k_shl_pick(const uint32_t* __restrict__ key, const uint32_t* order,
+                                                      int64_t m, uint32_t* __restrict__ gk, uint32_t* gv) {
+    const int64_t p = (int64_t)blockIdx.x * SHL_TPB + threadIdx.x;
+    if (p >= m) return;
+    const uint32_t r = order[p];
+    gk[p] = key[r];
+    gv[p] = r;
+}
+
+__global__ void __launch_bounds__(SHL_TPB) k_shl_gather(const uint32_t* __restrict__ idx, int64_t m,
+                                                        const uint32_t* __restrict__ klo,
+                                                        const uint32_t* __restrict__ khi, uint64_t* __restrict__ sseg) {
+    const int64_t p = (int64_t)blockIdx.x * SHL_TPB + threadIdx.x;
+    if (p >= m) return;
+    const uint32_t r = idx[p];
+    sseg[p] = shq_key((int32_t)khi[r], (int32_t)klo[r]);
+}
+
+__global__ void __launch_bounds__(SHL_TPB) k_shl_tile(const uint32_t* __restrict__ s32,
+                                                      const uint64_t* __restrict__ s64, int kbits, int64_t m,
+                                                      shq_table T, uint64_t* __restrict__ loc,
+                                                      uint64_t* __restrict__ tiles) {
+    __shared__ uint64_t wsum[SHL_TPB / 64];
+    const int64_t p0 = (int64_t)blockIdx.x * SHL_TILE + (int64_t)threadIdx.x * SHL_ITEMS;
+    uint64_t it[SHL_ITEMS];
+    uint64_t acc = 0;
+    uint64_t prev = (p0 > 0 && p0 <= m) ? shl_run_key(s32, s64, kbits, p0 - 1) : 0ull;
+#pragma unroll
+    for (int j = 0; j < SHL_ITEMS; j++) {
+        const int64_t p = p0 + j;
+        uint64_t x = 0;
+        if (p < m) {
+            const uint64_t sg = shl_run_key(s32, s64, kbits, p);
+            if (p == 0 || sg != prev) {
+                const int64_t slot = shq_find(T, sg);
+                const uint32_t c0 = slot >= 0 ? (uint32_t)T.state[slot * 2] : 0u;
+                x = ((uint64_t)p << 32) | c0;
+            }
+            prev = sg;
+        }
+        acc = shl_max(acc, x);
+        it[j] = acc;
+    }
+    uint64_t inc;
+    const uint64_t pre = shl_block_scan<SHL_TPB>(acc, wsum, &inc);
+#pragma unroll
+    for (int j = 0; j < SHL_ITEMS; j++) {
+        const int64_t p = p0 + j;
+        if (p < m) loc[p] = shl_max(pre, it[j]);
+    }
+    if (threadIdx.x == SHL_TPB - 1) tiles[blockIdx.x] = inc;
+}
+
+// exclusive max-scan of the tile aggregates, in place (one workgroup; a thread walks
+// its run of ceil(nt / SHL_CARRY_TPB) tiles)
+__global__ void __launch_bounds__(SHL_CARRY_TPB) k_shl_carry(uint64_t* __restrict__ tiles, int64_t nt) {
+    __shared__ uint64_t wsum[SHL_CARRY_TPB / 64];
+    const int64_t per = (nt + SHL_CARRY_TPB - 1) / SHL_CARRY_TPB;
+    const int64_t b = (int64_t)threadIdx.x * per;
+    uint64_t acc = 0;
+    for (int64_t t = b; t < b + per && t < nt; t++) acc = shl_max(acc, tiles[t]);
+    uint64_t inc;
+    uint64_t run = shl_block_scan<SHL_CARRY_TPB>(acc, wsum, &inc);
+    for (int64_t t = b; t < b + per && t < nt; t++) {
+        const uint64_t x = tiles[t];
+        tiles[t] = run;
+        run = shl_max(run, x);
+    }
+}
+
+// pk[p]: the run key at the last row of a limited query's run, SHQ_EMPTY elsewhere;
+// fin[2p]: that run's next counter (pk NULL: the caller carries nothing)
+__global__ void __launch_bounds__(SHL_TPB) k_shl_out(const uint32_t* __restrict__ s32,
+                                                     const uint64_t* __restrict__ s64, int kbits,
+                                                     const uint32_t* __restrict__ idx, int64_t m,
+                                                     const shl_rule* __restrict__ rules, int32_t n_rules,
+                                                     const uint64_t* __restrict__ loc,
+                                                     const uint64_t* __restrict__ tiles, uint8_t* __restrict__ keepb,
+                                                     uint64_t* __restrict__ pk, int64_t* __restrict__ fin) {
+    const int64_t p = (int64_t)blockIdx.x * SHL_TPB + threadIdx.x;
+    if (p >= m) return;
+    const uint64_t sg = shl_run_key(s32, s64, kbits, p);
+    const uint64_t v = shl_max(loc[p], tiles[p / SHL_TILE]);
+    const uint32_t c0 = (uint32_t)v;
+    const uint64_t j = (uint64_t)(p - (int64_t)(v >> 32)) + 1ull;
+    const int32_t q = (int32_t)(sg >> 32);
+    shl_rule R;
+    R.kind = SH_RATE_NONE;
+    R.n = 0;
+    if (q >= 0 && q < n_rules) R = rules[q];
+    keepb[idx[p]] = shl_keep(R, c0, j) ? 1 : 0;
+    if (!pk) return;
+    const bool tail = (p == m - 1 || shl_run_key(s32, s64, kbits, p + 1) != sg) && shl_limits(R);
+    pk[p] = tail ? sg : SHQ_EMPTY;
+    if (tail) {
+        fin[2 * p] = (int64_t)shl_next(R, c0, j);
+        fin[2 * p + 1] = 0;
+    }
+}
+
+// the keep bytes (row order) as ballot words and kept counts per tile of SHV_TILE rows
+__global__ void __launch_bounds__(SHV_TILE) k_shl_mark(const uint8_t* __restrict__ keepb, int64_t m,
+                                                       uint64_t* __restrict__ mask, uint32_t* __restrict__ cnt) {
+    __shared__ uint32_t wc[SHV_TILE / 64];
+    const int64_t r = (int64_t)blockIdx.x * SHV_TILE + threadIdx.x;
+    const bool keep = r < m && keepb[r] != 0;
+    const uint64_t b = __ballot(keep);
+    if ((threadIdx.x & 63) == 0) {
+        mask[r >> 6] = b;  // (the mask holds whole tiles: SHV_TILE / 64 words each)
+        wc[threadIdx.x >> 6] = (uint32_t)__popcll(b);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t s = 0;
+        for (int w = 0; w < SHV_TILE / 64; w++) s += wc[w];
+        cnt[blockIdx.x] = s;
+    }
+}
+
+// ---------------------------------------------------------------- host
+namespace {
+struct shl_ws {
+    uint32_t *klo, *khi, *idx, *gk, *kbuf[2], *vbuf[2], *hist, *stmp, *cnt, *off, *tmp;
+    uint64_t *sseg, *loc, *pk, *tiles, *mask;
+    int64_t* fin;
+    uint8_t* keepb;
+    int64_t bytes;
+};
+
+// the workspace's parts from `base` (NULL: sizes only), each 256-byte aligned
+shl_ws shl_layout(int64_t m, uint8_t* base) {
+    shl_ws W;
+    int64_t at = 0;
+    auto take = [&](int64_t bytes) {
+        uint8_t* r = base ? base + at : nullptr;
+        at += (bytes + 255) & ~(int64_t)255;
+        return (void*)r;
+    };
+    const int64_t rt = (m + 4095) / 4096, nt = (m + SHL_TILE - 1) / SHL_TILE, vt = (m + SHV_TILE - 1) / SHV_TILE;
+    W.sseg = (uint64_t*)take(m * 8);
+    W.loc = (uint64_t*)take(m * 8);
+    W.pk = (uint64_t*)take(m * 8);
+    W.fin = (int64_t*)take(m * 16);
+    W.tiles = (uint64_t*)take(nt * 8);
+    W.mask = (uint64_t*)take(vt * (SHV_TILE / 64) * 8);
+    W.klo = (uint32_t*)take(m * 4);
+    W.khi = (uint32_t*)take(m * 4);
+    W.idx = (uint32_t*)take(m * 4);
+    W.gk = (uint32_t*)take(m * 4);
+    for (int i = 0; i < 2; i++) W.kbuf[i] = (uint32_t*)take(m * 4);
+    for (int i = 0; i < 2; i++) W.vbuf[i] = (uint32_t*)take(m * 4);
+    W.hist = (uint32_t*)take(256 * rt * 4);
+    W.stmp = (uint32_t*)take((int64_t)shd_scan_tmp_words(256 * rt) * 4);
+    W.cnt = (uint32_t*)take(vt * 4);
+    W.off = (uint32_t*)take(vt * 4);
+    W.tmp = (uint32_t*)take((int64_t)shd_scan_tmp_words(vt) * 4);
+    W.keepb = (uint8_t*)take(m);
+    W.bytes = at;
+    return W;
+}
+
+int shl_ok() { return hipGetLastError() == hipSuccess ? 0 : -3; }
+}  // namespace
+
+extern "C" int64_t shl_limit_ws_words(int64_t m) { return shl_layout(m > 0 ? m : 1, nullptr).bytes / 4; }
+
+extern "C" int shl_limit(const shl_rule* rules, int32_t n_rules, int64_t m, int32_t n_out, const uint64_t* seq,
+                         const int64_t* vals, const int32_t* query, const int64_t* ts, const uint8_t* nulls,
+                         const int32_t* d_rowkey, const int32_t* d_keys, int32_t n_keys, uint64_t seq_base,
+                         const shq_table* T, uint64_t* o_seq, int64_t* o_vals, int32_t* o_query, int64_t* o_ts,
+                         uint8_t* o_nulls, uint32_t* ws, unsigned long long* d_kept, void* stream,
+                         const uint64_t** put_keys, const int64_t** put_state) {
+    hipStream_t st = (hipStream_t)stream;
+    if (put_keys) *put_keys = nullptr;
+    if (put_state) *put_state = nullptr;
+    if (!d_kept || m < 0 || m >= 0x7FFFFFFFll || n_out < 1 || n_out > SHV_MAX_OUT || n_rules < 1 || !rules) return -1;
+    if (T && T->cap > 0 && ((T->cap & (T->cap - 1)) || T->n_cols != 1 || !T->keys || !T->state)) return -1;
+    if (m == 0) return hipMemsetAsync(d_kept, 0, 8, st) == hipSuccess ? 0 : -3;
+    if (!vals || !o_vals || !ws || (o_seq && !seq) || (o_query && !query) || (o_ts && !ts) || (o_nulls && !nulls) ||
+        (!d_rowkey && d_keys && !seq) || ((uintptr_t)ws & 7))
+        return -1;
+    const shl_ws W = shl_layout(m, (uint8_t*)ws);
+    const unsigned g = (unsigned)((m + SHL_TPB - 1) / SHL_TPB);
+    const int64_t nt = (m + SHL_TILE - 1) / SHL_TILE, vt = (m + SHV_TILE - 1) / SHV_TILE;
+    int kbits = 0, qbits = 0;
+    while (kbits < 31 && ((int64_t)1 << kbits) < (int64_t)(n_keys < 1 ? 1 : n_keys)) kbits++;
+    while (qbits < 31 && ((int64_t)1 << qbits) < (int64_t)n_rules) qbits++;
+    if (!d_rowkey && !d_keys) kbits = 0;
+    if (!query) qbits = 0;
+    const bool wide = kbits + qbits > 32;
+    hipLaunchKernelGGL(k_shl_prep, dim3(g), dim3(SHL_TPB), 0, st, seq, m, query, d_rowkey, d_keys, seq_base, kbits,
+                       W.klo, wide ? W.khi : (uint32_t*)nullptr, W.idx);
+    if (shl_ok()) return -3;
+    const uint32_t* sidx = W.idx;
+    const uint32_t* s32 = W.klo;
+    const uint64_t* s64 = nullptr;
+    if (!wide) {
+        if (kbits + qbits > 0 &&
+            shd_sort_pairs(W.klo, W.idx, m, kbits + qbits, W.kbuf, W.vbuf, W.hist, W.stmp, stream, &s32, &sidx))
+            return -3;
+    } else {
+        const uint32_t* ko = nullptr;
+        if (shd_sort_pairs(W.klo, W.idx, m, kbits, W.kbuf, W.vbuf, W.hist, W.stmp, stream, &ko, &sidx)) return -3;
+        // (idx is free once the first sort has read it)
+        hipLaunchKernelGGL(k_shl_pick, dim3(g), dim3(SHL_TPB), 0, st, (const uint32_t*)W.khi, sidx, m, W.gk, W.idx);
+        if (shl_ok()) return -3;
+        if (shd_sort_pairs(W.gk, W.idx, m, qbits, W.kbuf, W.vbuf, W.hist, W.stmp, stream, &ko, &sidx)) return -3;
+        hipLaunchKernelGGL(k_shl_gather, dim3(g), dim3(SHL_TPB), 0, st, sidx, m, (const uint32_t*)W.klo,
+                           (const uint32_t*)W.khi, W.sseg);
+        s32 = nullptr;
+        s64 = W.sseg;
+    }
+    shq_table tab;
+    memset(&tab, 0, sizeof(tab));
+    if (T && T->cap > 0) tab = *T;
+    const bool put = put_keys && put_state;
+    hipLaunchKernelGGL(k_shl_tile, dim3((unsigned)nt), dim3(SHL_TPB), 0, st, s32, s64, kbits, m, tab, W.loc, W.tiles);
+    hipLaunchKernelGGL(k_shl_carry, dim3(1), dim3(SHL_CARRY_TPB), 0, st, W.tiles, nt);
+    hipLaunchKernelGGL(k_shl_out, dim3(g), dim3(SHL_TPB), 0, st, s32, s64, kbits, sidx, m, rules, n_rules,
+                       (const uint64_t*)W.loc, (const uint64_t*)W.tiles, W.keepb, put ? W.pk : (uint64_t*)nullptr,
+                       W.fin);
+    hipLaunchKernelGGL(k_shl_mark, dim3((unsigned)vt), dim3(SHV_TILE), 0, st, (const uint8_t*)W.keepb, m, W.mask,
+                       W.cnt);
+    if (shl_ok()) return -3;
+    if (shv_move_marked(m, n_out, seq, vals, query, ts, nulls, o_seq, o_vals, o_query, o_ts, o_nulls, W.mask, W.cnt,
+                        W.off, W.tmp, d_kept, stream))
+        return -3;
+    if (put) {
+        *put_keys = W.pk;
+        *put_state = W.fin;
+    }
+    return 0;
+}

@@ -208,6 +208,21 @@ class DeviceRunner:
         """device time of the last run's filter launches (mark, scan, move), ms"""
         return lib().shx_having_ms(self.handle.h)
 
+    def rate_status(self):
+        """1: the device pass (sh_rate.hip) applied the `output first|last every N events`
+        limiters of the last run, 0: there is none, or the general engine's selector did."""
+        return lib().shx_rate_status(self.handle.h)
+
+    def rate_rows(self):
+        """(rows in, rows kept) of the event limiters' pass in the last run"""
+        a, b = C.c_int64(0), C.c_int64(0)
+        lib().shx_rate_rows(self.handle.h, C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def rate_ms(self):
+        """device time of the last run's limiter launches (sorts, scan, move), ms"""
+        return lib().shx_rate_ms(self.handle.h)
+
     def last_error(self):
         return lib().sh_last_error(self.handle.h).decode()
 
