@@ -243,39 +243,41 @@ inline int shv_lower(const sh_query_desc* q, shv_prog* P) {
 
 // ---- the device filter (sh_having.hip): a stable compaction of ordered rows
 #define SHV_TILE 256  // rows per tile: one workgroup, one row per lane in the mark
+// A set of m ordered rows as parallel columns, to read and to write: vals holds
+// m x n_out raw values and nulls their null flags (NULL: none are null); seq, query,
+// ts and key (the row's partition key) hold one entry per row. Only vals is
+// mandatory. A pass moves a column iff its destination is set (NULL copies nothing)
+// and refuses (-1) a destination whose source column is NULL. The two sets never
+// overlap: a workgroup may write a destination another has yet to read.
+struct shw_rows {
+    const uint64_t* seq; const int64_t* vals; const int32_t* query;
+    const int64_t* ts; const uint8_t* nulls; const int32_t* key;
+};
+struct shw_rows_out {
+    uint64_t* seq; int64_t* vals; int32_t* query;
+    int64_t* ts; uint8_t* nulls; int32_t* key;
+};
 #ifdef __cplusplus
 extern "C" {
 #endif
 // 4-byte words of workspace for m rows: the ballot words (2 per 64 rows), the tiles'
 // kept counts and their exclusive scan, and the scan's own block sums
 int64_t shv_filter_ws_words(int64_t m);
-// Keeps row r of the m ordered rows iff progs[query[r]] (progs[0] when query is
+// Keeps row r of the m ordered rows of src iff progs[query[r]] (progs[0] when query is
 // NULL; a query id outside [0, n_progs) keeps the row) passes on its values
-// vals[r * n_out ..] and null flags nulls[r * n_out ..] (NULL: none are null). The
-// kept rows go, in order, to the o_* arrays (each as long as its source; seq, query,
-// ts and nulls are optional, and so is each of their o_* arrays: NULL copies nothing),
-// which must not overlap the sources: a workgroup may write a
-// destination another has yet to read. *d_kept (device, 8 bytes) takes the kept
+// vals[r * n_out ..] and null flags nulls[r * n_out ..]. The kept rows go, in order,
+// to dst (each column as long as its source). *d_kept (device, 8 bytes) takes the kept
 // count. 1 <= n_out <= SHV_MAX_OUT, m < 2^31; ws: shv_filter_ws_words(m) words.
 // All launches are asynchronous on `stream`. 0: launched, < 0: bad arguments.
-int shv_filter(const struct shv_prog* progs, int32_t n_progs, int64_t m, int32_t n_out, const uint64_t* seq,
-               const int64_t* vals, const int32_t* query, const int64_t* ts, const uint8_t* nulls, uint64_t* o_seq,
-               int64_t* o_vals, int32_t* o_query, int64_t* o_ts, uint8_t* o_nulls, uint32_t* ws,
-               unsigned long long* d_kept, void* stream);
-// shv_filter with one more optional column: key[r] (the row's partition key) moves to
-// o_key with the kept rows
-int shv_filter_keyed(const struct shv_prog* progs, int32_t n_progs, int64_t m, int32_t n_out, const uint64_t* seq,
-                     const int64_t* vals, const int32_t* query, const int64_t* ts, const uint8_t* nulls,
-                     const int32_t* key, uint64_t* o_seq, int64_t* o_vals, int32_t* o_query, int64_t* o_ts,
-                     uint8_t* o_nulls, int32_t* o_key, uint32_t* ws, unsigned long long* d_kept, void* stream);
+int shv_filter(const struct shv_prog* progs, int32_t n_progs, int64_t m, int32_t n_out, const struct shw_rows* src,
+               const struct shw_rows_out* dst, uint32_t* ws, unsigned long long* d_kept, void* stream);
 // The same compaction from ready marks (the event limiter's, sh_rate.hip): mask holds
 // one 64-bit ballot word per 64 rows (whole tiles of SHV_TILE rows: rows past m are 0),
 // cnt the kept rows of every tile; off [tiles] and tmp [shd_scan_tmp_words(tiles)] are
 // scratch. The tiles' counts are scanned and the kept rows moved as shv_filter does.
-int shv_move_marked(int64_t m, int32_t n_out, const uint64_t* seq, const int64_t* vals, const int32_t* query,
-                    const int64_t* ts, const uint8_t* nulls, uint64_t* o_seq, int64_t* o_vals, int32_t* o_query,
-                    int64_t* o_ts, uint8_t* o_nulls, const uint64_t* mask, const uint32_t* cnt, uint32_t* off,
-                    uint32_t* tmp, unsigned long long* d_kept, void* stream);
+int shv_move_marked(int64_t m, int32_t n_out, const struct shw_rows* src, const struct shw_rows_out* dst,
+                    const uint64_t* mask, const uint32_t* cnt, uint32_t* off, uint32_t* tmp,
+                    unsigned long long* d_kept, void* stream);
 #ifdef __cplusplus
 }
 #endif

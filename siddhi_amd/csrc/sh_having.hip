@@ -90,63 +90,38 @@ extern "C" int64_t shv_filter_ws_words(int64_t m) {
     return nt * (SHV_TILE / 64) * 2 + 2 * nt + (int64_t)shd_scan_tmp_words(nt) + 2;
 }
 
-static int shv_move(int64_t m, int32_t n_out, const uint64_t* seq, const int64_t* vals, const int32_t* query,
-                    const int64_t* ts, const uint8_t* nulls, const int32_t* key, uint64_t* o_seq, int64_t* o_vals,
-                    int32_t* o_query, int64_t* o_ts, uint8_t* o_nulls, int32_t* o_key, const uint64_t* mask,
-                    const uint32_t* cnt, uint32_t* off, uint32_t* tmp, unsigned long long* d_kept, void* stream);
-
-extern "C" int shv_filter(const shv_prog* progs, int32_t n_progs, int64_t m, int32_t n_out, const uint64_t* seq,
-                          const int64_t* vals, const int32_t* query, const int64_t* ts, const uint8_t* nulls,
-                          uint64_t* o_seq, int64_t* o_vals, int32_t* o_query, int64_t* o_ts, uint8_t* o_nulls,
-                          uint32_t* ws, unsigned long long* d_kept, void* stream) {
-    return shv_filter_keyed(progs, n_progs, m, n_out, seq, vals, query, ts, nulls, nullptr, o_seq, o_vals, o_query,
-                            o_ts, o_nulls, nullptr, ws, d_kept, stream);
-}
-
-extern "C" int shv_filter_keyed(const shv_prog* progs, int32_t n_progs, int64_t m, int32_t n_out, const uint64_t* seq,
-                                const int64_t* vals, const int32_t* query, const int64_t* ts, const uint8_t* nulls,
-                                const int32_t* key, uint64_t* o_seq, int64_t* o_vals, int32_t* o_query, int64_t* o_ts,
-                                uint8_t* o_nulls, int32_t* o_key, uint32_t* ws, unsigned long long* d_kept,
-                                void* stream) {
+extern "C" int shv_filter(const shv_prog* progs, int32_t n_progs, int64_t m, int32_t n_out, const shw_rows* src,
+                          const shw_rows_out* dst, uint32_t* ws, unsigned long long* d_kept, void* stream) {
     hipStream_t st = (hipStream_t)stream;
     if (!d_kept || m < 0 || m >= 0x7FFFFFFFll || n_out < 1 || n_out > SHV_MAX_OUT || n_progs < 1 || !progs) return -1;
     if (m == 0) return hipMemsetAsync(d_kept, 0, 8, st) == hipSuccess ? 0 : -3;
-    if (!vals || !o_vals || !ws || (o_seq && !seq) || (o_query && !query) || (o_ts && !ts) || (o_nulls && !nulls) ||
-        (o_key && !key) || ((uintptr_t)ws & 7))
+    // (a mismatched pair is refused before anything is launched)
+    if (!src || !dst || !src->vals || !dst->vals || !ws || (dst->seq && !src->seq) || (dst->query && !src->query) ||
+        (dst->ts && !src->ts) || (dst->nulls && !src->nulls) || (dst->key && !src->key) || ((uintptr_t)ws & 7))
         return -1;
     const int64_t nt = shv_tiles(m);
     uint64_t* mask = (uint64_t*)ws;
     uint32_t* cnt = ws + nt * (SHV_TILE / 64) * 2;
     uint32_t* off = cnt + nt;
     uint32_t* tmp = off + nt;
-    hipLaunchKernelGGL(k_shv_mark, dim3((unsigned)nt), dim3(SHV_TILE), 0, st, progs, n_progs, m, n_out, vals, query,
-                       nulls, mask, cnt);
+    hipLaunchKernelGGL(k_shv_mark, dim3((unsigned)nt), dim3(SHV_TILE), 0, st, progs, n_progs, m, n_out, src->vals,
+                       src->query, src->nulls, mask, cnt);
     if (hipGetLastError() != hipSuccess) return -3;
-    return shv_move(m, n_out, seq, vals, query, ts, nulls, key, o_seq, o_vals, o_query, o_ts, o_nulls, o_key,
-                    (const uint64_t*)mask, (const uint32_t*)cnt, off, tmp, d_kept, stream);
+    return shv_move_marked(m, n_out, src, dst, (const uint64_t*)mask, (const uint32_t*)cnt, off, tmp, d_kept, stream);
 }
 
-extern "C" int shv_move_marked(int64_t m, int32_t n_out, const uint64_t* seq, const int64_t* vals,
-                               const int32_t* query, const int64_t* ts, const uint8_t* nulls, uint64_t* o_seq,
-                               int64_t* o_vals, int32_t* o_query, int64_t* o_ts, uint8_t* o_nulls, const uint64_t* mask,
-                               const uint32_t* cnt, uint32_t* off, uint32_t* tmp, unsigned long long* d_kept,
-                               void* stream) {
-    return shv_move(m, n_out, seq, vals, query, ts, nulls, nullptr, o_seq, o_vals, o_query, o_ts, o_nulls, nullptr, mask,
-                    cnt, off, tmp, d_kept, stream);
-}
-
-static int shv_move(int64_t m, int32_t n_out, const uint64_t* seq, const int64_t* vals, const int32_t* query,
-                    const int64_t* ts, const uint8_t* nulls, const int32_t* key, uint64_t* o_seq, int64_t* o_vals,
-                    int32_t* o_query, int64_t* o_ts, uint8_t* o_nulls, int32_t* o_key, const uint64_t* mask,
-                    const uint32_t* cnt, uint32_t* off, uint32_t* tmp, unsigned long long* d_kept, void* stream) {
+extern "C" int shv_move_marked(int64_t m, int32_t n_out, const shw_rows* src, const shw_rows_out* dst,
+                               const uint64_t* mask, const uint32_t* cnt, uint32_t* off, uint32_t* tmp,
+                               unsigned long long* d_kept, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    if (!d_kept || m <= 0 || m >= 0x7FFFFFFFll || n_out < 1 || n_out > SHV_MAX_OUT || !vals || !o_vals || !mask ||
-        !cnt || !off || !tmp || (o_seq && !seq) || (o_query && !query) || (o_ts && !ts) || (o_nulls && !nulls) ||
-        (o_key && !key))
+    if (!d_kept || m <= 0 || m >= 0x7FFFFFFFll || n_out < 1 || n_out > SHV_MAX_OUT || !src || !dst || !src->vals ||
+        !dst->vals || !mask || !cnt || !off || !tmp || (dst->seq && !src->seq) || (dst->query && !src->query) ||
+        (dst->ts && !src->ts) || (dst->nulls && !src->nulls) || (dst->key && !src->key))
         return -1;
     const int64_t nt = shv_tiles(m);
     if (shd_exclusive_scan(cnt, off, nt, tmp, stream)) return -3;
-    hipLaunchKernelGGL(k_shv_move, dim3((unsigned)nt), dim3(SHV_TILE), 0, st, n_out, seq, vals, query, ts, nulls, o_seq,
-                       o_vals, o_query, o_ts, o_nulls, mask, cnt, (const uint32_t*)off, d_kept, key, o_key);
+    hipLaunchKernelGGL(k_shv_move, dim3((unsigned)nt), dim3(SHV_TILE), 0, st, n_out, src->seq, src->vals, src->query,
+                       src->ts, src->nulls, dst->seq, dst->vals, dst->query, dst->ts, dst->nulls, mask, cnt,
+                       (const uint32_t*)off, d_kept, src->key, dst->key);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }

@@ -845,12 +845,12 @@ int sh_compile(const sh_app_desc* app, sh_handle** out) {
     }
     if (h->has_rules && upload_rules(h)) return SH_E_OOM;
     if (h->hv_on) {
-        if (h->hv_d_progs.ensure(h->hv_progs.size() * sizeof(shv_prog)) || h->hv_kept.ensure(64))
+        if (h->hv_d_progs.ensure(h->hv_progs.size() * sizeof(shv_prog)) || h->hv.kept.ensure(64))
             return fail(h, SH_E_OOM, "hipMalloc failed");
         hipMemcpy(h->hv_d_progs.p, h->hv_progs.data(), h->hv_progs.size() * sizeof(shv_prog), hipMemcpyHostToDevice);
     }
     if (h->rl_on) {
-        if (h->rl_d_rules.ensure(h->rl_rules.size() * sizeof(shl_rule)) || h->rl_kept.ensure(64))
+        if (h->rl_d_rules.ensure(h->rl_rules.size() * sizeof(shl_rule)) || h->rl.kept.ensure(64))
             return fail(h, SH_E_OOM, "hipMalloc failed");
         hipMemcpy(h->rl_d_rules.p, h->rl_rules.data(), h->rl_rules.size() * sizeof(shl_rule), hipMemcpyHostToDevice);
     }
@@ -926,17 +926,16 @@ void sh_destroy(sh_handle* h) {
             for (auto& c : R.col) c.release();
         }
         h->rc_klast.release();
-        h->ag_keys.release();
-        h->ag_state.release();
-        h->ag_ctl.release();
+        h->ag_tab.release();
         h->rc_okey.release();
         h->rc_ws.release();
         h->rc_oq.release();
         h->rc_ots.release();
-        DevBuf* hvb[] = {&h->hv_d_progs, &h->hv_ws, &h->hv_kept, &h->hv_seq, &h->hv_q, &h->hv_ts, &h->hv_vals, &h->hv_key,
-                         &h->rl_d_rules, &h->rl_ws, &h->rl_kept, &h->rl_seq, &h->rl_q, &h->rl_ts, &h->rl_vals,
-                         &h->rl_keys, &h->rl_state, &h->rl_ctl};
-        for (DevBuf* b : hvb) b->release();
+        h->hv_d_progs.release();
+        h->rl_d_rules.release();
+        h->hv.release();
+        h->rl.release();
+        h->rl_tab.release();
         for (auto& st : h->stores) {
             for (auto& c : st.cols) c.release();
             for (auto& c : st.nuls) c.release();
@@ -944,10 +943,6 @@ void sh_destroy(sh_handle* h) {
         for (auto& e : h->ev)
             if (e) hipEventDestroy(e);
         for (auto& e : h->bk_ev)
-            if (e) hipEventDestroy(e);
-        for (auto& e : h->hv_ev)
-            if (e) hipEventDestroy(e);
-        for (auto& e : h->rl_ev)
             if (e) hipEventDestroy(e);
         if (h->bk_side) hipStreamDestroy(h->bk_side);
         hipStreamDestroy(h->own_stream);
@@ -1667,16 +1662,17 @@ static int run_device_post(sh_handle* h, sh_device_run* run) {
     uint64_t* dst_seq = run->d_out_seq;
     int32_t* dst_q = run->d_out_query;
     const bool want_q = dst_q != nullptr || h->hv_progs.size() > 1 || h->rl_rules.size() > 1;
-    const bool both = h->hv_on && h->rl_on;
     // the limiters key a partitioned app's rows by their trigger events: sequence numbers
     const bool want_seq = dst_seq != nullptr || (h->rl_on && h->partitioned);
     if (!dst_vals) return fail(h, SH_E_INVALID_ARG, "sh_run_device: d_out_values is NULL");
-    if (h->hv_vals.ensure_fresh(cap * no * 8) || h->hv_seq.ensure_fresh(cap * 8) ||
-        (want_q && h->hv_q.ensure_fresh(cap * 4)))
+    // (the engines write `having`'s buffers, so with both passes on the intermediate rows
+    // are in the limiters')
+    RowStage& E = h->hv;
+    if (E.vals.ensure_fresh(cap * no * 8) || E.seq.ensure_fresh(cap * 8) || (want_q && E.q.ensure_fresh(cap * 4)))
         return fail(h, SH_E_OOM, "row filter buffers");
-    run->d_out_values = h->hv_vals.as<int64_t>();
-    run->d_out_seq = h->hv_seq.as<uint64_t>();
-    run->d_out_query = want_q ? h->hv_q.as<int32_t>() : nullptr;
+    run->d_out_values = E.vals.as<int64_t>();
+    run->d_out_seq = E.seq.as<uint64_t>();
+    run->d_out_query = want_q ? E.q.as<int32_t>() : nullptr;
     bool general = false;
     rc = run_engines(h, run, &general);
     run->d_out_values = dst_vals;
@@ -1688,51 +1684,27 @@ static int run_device_post(sh_handle* h, sh_device_run* run) {
     if (general) {
         // the general engine's selector applied `having` and the limiters: its rows as they are
         if (m > 0) {
-            hipMemcpyAsync(dst_vals, h->hv_vals.p, (size_t)m * no * 8, hipMemcpyDeviceToDevice, h->stream);
-            if (dst_seq) hipMemcpyAsync(dst_seq, h->hv_seq.p, (size_t)m * 8, hipMemcpyDeviceToDevice, h->stream);
-            if (dst_q) hipMemcpyAsync(dst_q, h->hv_q.p, (size_t)m * 4, hipMemcpyDeviceToDevice, h->stream);
+            hipMemcpyAsync(dst_vals, E.vals.p, (size_t)m * no * 8, hipMemcpyDeviceToDevice, h->stream);
+            if (dst_seq) hipMemcpyAsync(dst_seq, E.seq.p, (size_t)m * 8, hipMemcpyDeviceToDevice, h->stream);
+            if (dst_q) hipMemcpyAsync(dst_q, E.q.p, (size_t)m * 4, hipMemcpyDeviceToDevice, h->stream);
             if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(h, SH_E_HIP, "device error copying rows");
         }
         return SH_OK;
     }
-    const uint64_t* src_seq = h->hv_seq.as<uint64_t>();
-    const int64_t* src_vals = h->hv_vals.as<int64_t>();
-    const int32_t* src_q = want_q ? h->hv_q.as<int32_t>() : nullptr;
-    unsigned long long kept = 0;
-    if (h->hv_on) {
-        // (with limiters behind it: into their source buffers)
-        if (both && (h->rl_vals.ensure_fresh(cap * no * 8) || h->rl_seq.ensure_fresh(cap * 8) ||
-                     (want_q && h->rl_q.ensure_fresh(cap * 4))))
-            return fail(h, SH_E_OOM, "row filter buffers");
-        uint64_t* o_seq = both ? (want_seq ? h->rl_seq.as<uint64_t>() : nullptr) : dst_seq;
-        int64_t* o_vals = both ? h->rl_vals.as<int64_t>() : dst_vals;
-        int32_t* o_q = both ? (want_q ? h->rl_q.as<int32_t>() : nullptr) : dst_q;
-        rc = having_filter(h, m, no, src_seq, src_vals, src_q, nullptr, o_seq, o_vals, o_q, nullptr);
-        if (rc) return rc;
-        hipMemcpyAsync(&kept, h->hv_kept.p, 8, hipMemcpyDeviceToHost, h->stream);
-        if (hipStreamSynchronize(h->stream) != hipSuccess || (int64_t)kept > m)
-            return fail(h, SH_E_HIP, "device error in the having filter");
-        h->hv_last = 1;
-        h->hv_rows_in = m;
-        h->hv_rows_kept = (int64_t)kept;
-        m = (int64_t)kept;
-        src_seq = o_seq;
-        src_vals = o_vals;
-        src_q = o_q;
-    }
-    if (h->rl_on) {
-        const int32_t nkeys = h->partitioned ? std::max(1, run->n_keys) : 1;
-        rc = rate_limit(h, m, no, src_seq, src_vals, src_q, nullptr, nullptr, h->partitioned ? run->d_keys : nullptr,
-                        nkeys, nullptr, dst_seq, dst_vals, dst_q, nullptr, nullptr, nullptr);
-        if (rc) return rc;
-        hipMemcpyAsync(&kept, h->rl_kept.p, 8, hipMemcpyDeviceToHost, h->stream);
-        if (hipStreamSynchronize(h->stream) != hipSuccess || (int64_t)kept > m)
-            return fail(h, SH_E_HIP, "device error in the event limiters");
-        h->rl_last = 1;
-        h->rl_rows_in = m;
-        h->rl_rows_kept = (int64_t)kept;
-    }
-    run->out_count = (int64_t)kept;
+    const shw_rows_out end{dst_seq, dst_vals, dst_q, nullptr, nullptr, nullptr};
+    RowPost P;
+    P.src = shw_rows{want_seq ? E.seq.as<uint64_t>() : nullptr, E.vals.as<int64_t>(),
+                     want_q ? E.q.as<int32_t>() : nullptr, nullptr, nullptr, nullptr};
+    P.m = m;
+    P.n_out = no;
+    P.end = &end;
+    P.mid = &h->rl;
+    P.room = cap;
+    P.d_keys = h->partitioned ? run->d_keys : nullptr;
+    P.n_keys = h->partitioned ? std::max(1, run->n_keys) : 1;
+    rc = row_post(h, P);
+    if (rc) return rc;
+    run->out_count = P.after_rate;
     return SH_OK;
 }
 
@@ -1744,7 +1716,7 @@ static int run_device_impl(sh_handle* h, sh_device_run* run) {
     // were written there (the handle's own stream is non-blocking and would not
     // wait for them)
     h->stream = (hipStream_t)run->stream;
-    h->hv_last = h->rl_last = 0;
+    h->hv.last = h->rl.last = 0;
     if (h->hv_on || h->rl_on) return run_device_post(h, run);
     bool general = false;
     return run_engines(h, run, &general);
@@ -1901,39 +1873,23 @@ int shx_agg_status(sh_handle* h) { return h ? h->agg_last : 0; }
 
 // `having` of the last sh_run_device or streaming step: 1 the device row filter
 // (sh_having.hip) applied it, 0 there is none or the general engine's selector did
-int shx_having_status(sh_handle* h) { return h ? h->hv_last : 0; }
+int shx_having_status(sh_handle* h) { return h ? h->hv.last : 0; }
 // ... and that filter's rows in and rows kept (0, 0 when it did not run)
 int shx_having_rows(sh_handle* h, int64_t* rows_in, int64_t* rows_kept) {
-    if (!h) return 0;
-    if (rows_in) *rows_in = h->hv_last ? h->hv_rows_in : 0;
-    if (rows_kept) *rows_kept = h->hv_last ? h->hv_rows_kept : 0;
-    return h->hv_last;
+    return h ? h->hv.rows(rows_in, rows_kept) : 0;
 }
-
 // device time of the last run's or step's filter launches (mark, scan, move), ms
-double shx_having_ms(sh_handle* h) {
-    float ms = 0.f;
-    if (!h || !h->hv_last || !h->hv_ev[1] || hipEventElapsedTime(&ms, h->hv_ev[0], h->hv_ev[1]) != hipSuccess) return 0.0;
-    return ms;
-}
+double shx_having_ms(sh_handle* h) { return h ? h->hv.ms() : 0.0; }
 
 // the event limiters of the last sh_run_device or streaming step: 1 the device pass
-// (sh_rate.hip) applied them, 0 there is none or the general engine's selector did
-int shx_rate_status(sh_handle* h) { return h ? h->rl_last : 0; }
-// ... and that pass's rows in and rows kept (0, 0 when it did not run)
+// (sh_rate.hip) applied them, 0 there is none or the general engine's selector did;
+// that pass's rows in and rows kept (0, 0 when it did not run); and the device time
+// of its launches (sorts, scan, move), ms
+int shx_rate_status(sh_handle* h) { return h ? h->rl.last : 0; }
 int shx_rate_rows(sh_handle* h, int64_t* rows_in, int64_t* rows_kept) {
-    if (!h) return 0;
-    if (rows_in) *rows_in = h->rl_last ? h->rl_rows_in : 0;
-    if (rows_kept) *rows_kept = h->rl_last ? h->rl_rows_kept : 0;
-    return h->rl_last;
+    return h ? h->rl.rows(rows_in, rows_kept) : 0;
 }
-
-// device time of the last run's or step's limiter launches (sorts, scan, move), ms
-double shx_rate_ms(sh_handle* h) {
-    float ms = 0.f;
-    if (!h || !h->rl_last || !h->rl_ev[1] || hipEventElapsedTime(&ms, h->rl_ev[0], h->rl_ev[1]) != hipSuccess) return 0.0;
-    return ms;
-}
+double shx_rate_ms(sh_handle* h) { return h ? h->rl.ms() : 0.0; }
 
 // the compiled-program fingerprint a snapshot image carries (0: no handle)
 uint64_t shx_fingerprint(sh_handle* h) { return h ? h->fp : 0; }
@@ -1953,10 +1909,10 @@ int shx_rules_carry(sh_handle* h, int64_t* partials, int64_t* rows) {
 // return value, saturated), and the table's capacity in entries
 int shx_rules_agg_carry(sh_handle* h, int64_t* entries) {
     if (!h) return 0;
-    if (entries) *entries = h->ag_entries;
-    return (int)std::min<int64_t>(h->ag_entries, 0x7FFFFFFF);
+    if (entries) *entries = h->ag_tab.entries;
+    return (int)std::min<int64_t>(h->ag_tab.entries, 0x7FFFFFFF);
 }
-int64_t shx_rules_agg_capacity(sh_handle* h) { return h ? h->ag_cap : 0; }
+int64_t shx_rules_agg_capacity(sh_handle* h) { return h ? h->ag_tab.cap : 0; }
 
 // SH_HOST_PROF phase clocks of a streaming handle (ms and counts, SH_HP_N phases)
 int shx_host_profile(sh_handle* h, double* ms, int64_t* n, int cap) {

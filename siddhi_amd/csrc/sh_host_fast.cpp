@@ -100,11 +100,9 @@ shq_table carry_table(const CarryTab& C) {
     return T;
 }
 
-shq_table agg_carry_table(sh_handle* h) { return carry_table(agg_tab(h)); }
-
 // room for `add` more entries at no more than half full: the table is rebuilt at
 // (at least) double capacity, every entry kept -- the one place a step costs O(table)
-int carry_reserve(sh_handle* h, const CarryTab& C, int64_t add, int n_cols) {
+int carry_reserve(sh_handle* h, CarryTab& C, int64_t add, int n_cols) {
     hipStream_t st = h->stream;
     if (C.ctl.ensure_fresh(64)) return SH_E_OOM;
     const int64_t need = (C.entries + add) * 2;
@@ -146,10 +144,8 @@ int carry_reserve(sh_handle* h, const CarryTab& C, int64_t add, int n_cols) {
     return SH_OK;
 }
 
-int agg_carry_reserve(sh_handle* h, int64_t add, int n_cols) { return carry_reserve(h, agg_tab(h), add, n_cols); }
-
 // the table emptied and filled with n entries (restore; n = 0: a fresh handle's)
-int carry_load(sh_handle* h, const CarryTab& C, int nc, const uint64_t* keys, const int64_t* state, int64_t n) {
+int carry_load(sh_handle* h, CarryTab& C, int nc, const uint64_t* keys, const int64_t* state, int64_t n) {
     hipStream_t st = h->stream;
     C.entries = 0;
     if (C.cap > 0) hipMemsetAsync(C.keys.p, 0xFF, (size_t)C.cap * 8, st);
@@ -181,10 +177,6 @@ int carry_load(sh_handle* h, const CarryTab& C, int nc, const uint64_t* keys, co
     return SH_OK;
 }
 
-int agg_carry_load(sh_handle* h, const uint64_t* keys, const int64_t* state, int64_t n) {
-    return carry_load(h, agg_tab(h), agg_carry_cols(h), keys, state, n);
-}
-
 // the live entries sorted by table key, each with its per-column state
 int carry_dump(const CarryTab& C, std::vector<uint64_t>& keys, std::vector<int64_t>& state) {
     keys.clear();
@@ -205,10 +197,6 @@ int carry_dump(const CarryTab& C, std::vector<uint64_t>& keys, std::vector<int64
         state.insert(state.end(), s.begin() + i * w, s.begin() + (i + 1) * w);
     }
     return (int64_t)keys.size() == C.entries ? SH_OK : SH_E_HIP;
-}
-
-int agg_carry_dump(sh_handle* h, std::vector<uint64_t>& keys, std::vector<int64_t>& state) {
-    return carry_dump(agg_tab(h), keys, state);
 }
 
 // sh_run_device on a rule set beyond the general engine's table whose additions
@@ -664,56 +652,126 @@ int rules_stage(sh_handle* h, const sh_batch* b) {
 }
 
 // the device row filter (sh_having.hip) over m ordered raw rows, launched on the
-// handle's stream: the kept rows go to the o_* buffers, their count to h->hv_kept
-int having_filter(sh_handle* h, int64_t m, int n_out, const uint64_t* seq, const int64_t* vals, const int32_t* query,
-                  const int64_t* ts, uint64_t* o_seq, int64_t* o_vals, int32_t* o_query, int64_t* o_ts,
-                  const int32_t* key, int32_t* o_key) {
-    if (h->hv_ws.ensure_fresh((size_t)shv_filter_ws_words(m) * 4) || h->hv_kept.ensure(64))
+// handle's stream: the kept rows go to dst, their count to h->hv.kept
+int having_filter(sh_handle* h, int64_t m, int n_out, const shw_rows& src, const shw_rows_out& dst) {
+    RowStage& S = h->hv;
+    if (S.ws.ensure_fresh((size_t)shv_filter_ws_words(m) * 4) || S.kept.ensure(64))
         return fail(h, SH_E_OOM, "having filter workspace");
-    for (auto& e : h->hv_ev)
+    for (auto& e : S.ev)
         if (!e) hipEventCreate(&e);
-    hipEventRecord(h->hv_ev[0], h->stream);
-    if (shv_filter_keyed(h->hv_d_progs.as<shv_prog>(), (int32_t)h->hv_progs.size(), m, n_out, seq, vals, query, ts,
-                         nullptr, key, o_seq, o_vals, o_query, o_ts, nullptr, o_key, h->hv_ws.as<uint32_t>(),
-                         h->hv_kept.as<unsigned long long>(), h->stream))
+    hipEventRecord(S.ev[0], h->stream);
+    if (shv_filter(h->hv_d_progs.as<shv_prog>(), (int32_t)h->hv_progs.size(), m, n_out, &src, &dst, S.ws.as<uint32_t>(),
+                   S.kept.as<unsigned long long>(), h->stream))
         return fail(h, SH_E_HIP, "having filter launch failed");
-    hipEventRecord(h->hv_ev[1], h->stream);
+    hipEventRecord(S.ev[1], h->stream);
     return SH_OK;
 }
 
-int rate_limit(sh_handle* h, int64_t m, int n_out, const uint64_t* seq, const int64_t* vals, const int32_t* query,
-               const int64_t* ts, const int32_t* rowkey, const int32_t* keys, int32_t n_keys, const shq_table* T,
-               uint64_t* o_seq, int64_t* o_vals, int32_t* o_query, int64_t* o_ts, const uint64_t** put_keys,
-               const int64_t** put_state) {
-    if (h->rl_ws.ensure_fresh((size_t)shl_limit_ws_words(m) * 4) || h->rl_kept.ensure(64))
+int rate_limit(sh_handle* h, int64_t m, int n_out, const shw_rows& src, const int32_t* keys, int32_t n_keys,
+               const shq_table* T, const shw_rows_out& dst, const uint64_t** put_keys, const int64_t** put_state) {
+    RowStage& S = h->rl;
+    if (S.ws.ensure_fresh((size_t)shl_limit_ws_words(m) * 4) || S.kept.ensure(64))
         return fail(h, SH_E_OOM, "event limiter workspace");
-    for (auto& e : h->rl_ev)
+    for (auto& e : S.ev)
         if (!e) hipEventCreate(&e);
-    hipEventRecord(h->rl_ev[0], h->stream);
-    if (shl_limit(h->rl_d_rules.as<shl_rule>(), (int32_t)h->rl_rules.size(), m, n_out, seq, vals, query, ts, nullptr,
-                  rowkey, keys, n_keys, 0, T, o_seq, o_vals, o_query, o_ts, nullptr, h->rl_ws.as<uint32_t>(),
-                  h->rl_kept.as<unsigned long long>(), h->stream, put_keys, put_state))
+    hipEventRecord(S.ev[0], h->stream);
+    if (shl_limit(h->rl_d_rules.as<shl_rule>(), (int32_t)h->rl_rules.size(), m, n_out, &src, keys, n_keys, 0, T, &dst,
+                  S.ws.as<uint32_t>(), S.kept.as<unsigned long long>(), h->stream, put_keys, put_state))
         return fail(h, SH_E_HIP, "event limiter launch failed");
-    hipEventRecord(h->rl_ev[1], h->stream);
+    hipEventRecord(S.ev[1], h->stream);
     return SH_OK;
 }
 
-// the staged calls are dropped: a refused step leaves the handle where it was
-// before them (counters included), with the carried state untouched
-static int rules_step_fail(sh_handle* h, int code, const char* msg) {
+// the host output queue at `rows` rows (a step appends its rows, or takes them back)
+static void out_queue_rows(sh_handle* h, size_t rows) {
+    h->o_query.resize(rows);
+    h->o_seq.resize(rows);
+    h->o_ts.resize(rows);
+    h->o_vals.resize(rows * h->n_out);
+    h->o_nulls.resize(rows * h->n_out, 0);
+}
+
+// a step's staged calls are behind it: the staging emptied, and the counters where
+// the next calls start (the step's end, or -- a refused step -- where they were before)
+static void rules_unstage(sh_handle* h) {
     h->rq_ts.clear();
     h->rq_key.clear();
     h->rq_seq.clear();
     h->rq_run.clear();
     for (auto& c : h->rq_col) c.clear();
     h->rq_run_next = 0;
-    h->rq_nullbit = false;
+    h->seq_staged0 = h->seq_next;
+    h->rq_call0 = h->rq_call;
+}
+
+// the staged calls are dropped: a refused step leaves the handle where it was
+// before them (counters included), with the carried state untouched
+static int rules_step_fail(sh_handle* h, int code, const char* msg) {
     h->seq_next = h->seq_staged0;
     h->rq_call = h->rq_call0;
+    rules_unstage(h);
+    h->rq_nullbit = false;
     h->step_seqs = nullptr;
     h->step_ots = nullptr;
     h->step_okey = nullptr;
     return fail(h, code, msg);
+}
+
+// the stage's own destination for `rows` rows in S's buffers: every column src has
+static int stage_rows(RowStage& S, size_t rows, int n_out, const shw_rows& src, bool with_key, shw_rows_out* o) {
+    if (S.vals.ensure_fresh(rows * n_out * 8) || (src.seq && S.seq.ensure_fresh(rows * 8)) ||
+        (src.query && S.q.ensure_fresh(rows * 4)) || (src.ts && S.ts.ensure_fresh(rows * 8)) ||
+        (with_key && S.key.ensure_fresh(rows * 4)))
+        return SH_E_OOM;
+    *o = shw_rows_out{src.seq ? S.seq.as<uint64_t>() : nullptr,
+                      S.vals.as<int64_t>(),
+                      src.query ? S.q.as<int32_t>() : nullptr,
+                      src.ts ? S.ts.as<int64_t>() : nullptr,
+                      nullptr,
+                      with_key ? S.key.as<int32_t>() : nullptr};
+    return SH_OK;
+}
+
+int row_post(sh_handle* h, RowPost& P) {
+    auto refuse = [&](int code, const char* msg) { return P.step ? rules_step_fail(h, code, msg) : fail(h, code, msg); };
+    shw_rows src = P.src;
+    int64_t m = P.m;
+    for (int pass = 0; pass < 2; pass++) {
+        const bool rate = pass == 1;
+        if (rate) P.after_having = m;
+        if (!(rate ? h->rl_on : h->hv_on) || (rate && P.step && m == 0)) continue;
+        RowStage& S = rate ? h->rl : h->hv;
+        const bool last = rate || !h->rl_on;
+        shw_rows_out dst;
+        if (last && P.end)
+            dst = *P.end;
+        else if (stage_rows(last ? S : *P.mid, P.room ? P.room : (size_t)m, P.n_out, src, !last && src.key, &dst))
+            return refuse(SH_E_OOM, !P.step ? "row filter buffers" : rate ? "event limiter buffers" : "having filter buffers");
+        int rc;
+        if (rate) {
+            shq_table T;
+            if (P.tab) T = carry_table(*P.tab);
+            rc = rate_limit(h, m, P.n_out, src, P.d_keys, P.n_keys, P.tab ? &T : nullptr, dst,
+                            P.tab ? &P.put_keys : nullptr, P.tab ? &P.put_state : nullptr);
+        } else {
+            rc = having_filter(h, m, P.n_out, src, dst);
+        }
+        if (rc) return P.step ? rules_step_fail(h, SH_E_HIP, h->err.c_str()) : rc;
+        unsigned long long kept = 0;
+        hipMemcpyAsync(&kept, S.kept.p, 8, hipMemcpyDeviceToHost, h->stream);
+        if (hipStreamSynchronize(h->stream) != hipSuccess || (int64_t)kept > m)
+            return refuse(SH_E_HIP, rate ? "device error in the event limiters" : "device error in the having filter");
+        if (!P.step) {
+            S.last = 1;
+            S.rows_in = m;
+            S.rows_kept = (int64_t)kept;
+        }
+        m = (int64_t)kept;
+        src = shw_rows{dst.seq, dst.vals, dst.query, dst.ts, dst.nulls, dst.key};
+    }
+    P.after_rate = m;
+    P.out = src;
+    return SH_OK;
 }
 
 // One device step over everything staged: the key-segment scans run over the
@@ -830,8 +888,8 @@ int rules_step(sh_handle* h) {
     int32_t flag = 0;
     const uint64_t* ag_pk = nullptr;   // carried aggregates: the step's segment heads and
     const int64_t* ag_fin = nullptr;   // their final states (shc_running)
-    const uint64_t* rl_pk = nullptr;   // event limiters: the step's runs and their next
-    const int64_t* rl_fin = nullptr;   // counters (shl_limit)
+    RowPost post;                      // event limiters: the step's runs and their next
+                                       // counters (shl_limit) come back in put_keys / put_state
     hipMemcpyAsync(&lo, off + (n - 1), 4, hipMemcpyDeviceToHost, st);
     hipMemcpyAsync(&lc, cnt + (n - 1), 4, hipMemcpyDeviceToHost, st);
     hipMemcpyAsync(&npairs, soff + n, 4, hipMemcpyDeviceToHost, st);
@@ -880,13 +938,13 @@ int rules_step(sh_handle* h) {
             // rebuild keeps every entry, so a refusal further down loses nothing)
             agg_desc(h->r_agg, h->r_argt, no, &AD);
             if ((sorted && h->rc_okey.ensure_fresh((size_t)m * 4)) ||
-                h->a_scratch.ensure_fresh((size_t)shc_scratch_bytes(m, AD.n_cols)) || agg_carry_reserve(h, m, AD.n_cols))
+                h->a_scratch.ensure_fresh((size_t)shc_scratch_bytes(m, AD.n_cols)) || carry_reserve(h, h->ag_tab, m, AD.n_cols))
                 return rules_step_fail(h, SH_E_OOM, "carried aggregates");
             h->step_okey = sorted ? h->rc_okey.as<int32_t>() : nullptr;
         }
         if (h->rl_on) {
             // the limiters' counters: keyed and reserved as the aggregates' states are
-            if ((sorted && h->rc_okey.ensure_fresh((size_t)m * 4)) || carry_reserve(h, rate_tab(h), m, 1))
+            if ((sorted && h->rc_okey.ensure_fresh((size_t)m * 4)) || carry_reserve(h, h->rl_tab, m, 1))
                 return rules_step_fail(h, SH_E_OOM, "carried limiter counters");
             h->step_okey = sorted ? h->rc_okey.as<int32_t>() : nullptr;
         }
@@ -901,53 +959,28 @@ int rules_step(sh_handle* h) {
         // the running values, one addition at a time from each segment's carried state
         // (the table itself moves last, below)
         if (h->r_aggp) {
-            const shq_table T = agg_carry_table(h);
+            const shq_table T = carry_table(h->ag_tab);
             if (shc_running(h->w_oseq.as<uint64_t>(), h->w_ovals.as<int64_t>(), no, m, h->rc_oq.as<int32_t>(),
                             (int32_t)h->r_rules.size(), sorted ? h->rc_okey.as<int32_t>() : nullptr, nullptr, nkeys, 0,
                             &AD, &T, h->a_scratch.p, st, &ag_pk, &ag_fin))
                 return rules_step_fail(h, SH_E_HIP, "carried aggregate launch failed");
         }
-        // `having`: the rows handed to the host queue are the kept ones, from the
-        // filter's own buffers (the aggregate table below takes every row's state)
-        if (h->hv_on) {
-            if (h->hv_seq.ensure_fresh((size_t)m * 8) || h->hv_ts.ensure_fresh((size_t)m * 8) ||
-                h->hv_q.ensure_fresh((size_t)m * 4) || h->hv_vals.ensure_fresh((size_t)m * no * 8) ||
-                (rl_keyed && h->hv_key.ensure_fresh((size_t)m * 4)))
-                return rules_step_fail(h, SH_E_OOM, "having filter buffers");
-            // (the limiters behind it key the kept rows: their keys move with them)
-            if (having_filter(h, m, no, h->w_oseq.as<uint64_t>(), h->w_ovals.as<int64_t>(), h->rc_oq.as<int32_t>(),
-                              h->rc_ots.as<int64_t>(), h->hv_seq.as<uint64_t>(), h->hv_vals.as<int64_t>(),
-                              h->hv_q.as<int32_t>(), h->hv_ts.as<int64_t>(),
-                              rl_keyed ? h->rc_okey.as<int32_t>() : nullptr, rl_keyed ? h->hv_key.as<int32_t>() : nullptr))
-                return rules_step_fail(h, SH_E_HIP, h->err.c_str());
-            unsigned long long kept = 0;
-            hipMemcpyAsync(&kept, h->hv_kept.p, 8, hipMemcpyDeviceToHost, st);
-            if (hipStreamSynchronize(st) != hipSuccess || (int64_t)kept > m)
-                return rules_step_fail(h, SH_E_HIP, "device error in the having filter");
-            mk = (int64_t)kept;
-        }
-        // the event limiters, on the rows `having` kept, from each run's carried counter
-        // (the counters' table moves last, below)
-        ml = mk;
-        if (h->rl_on && ml > 0) {
-            if (h->rl_seq.ensure_fresh((size_t)ml * 8) || h->rl_ts.ensure_fresh((size_t)ml * 8) ||
-                h->rl_q.ensure_fresh((size_t)ml * 4) || h->rl_vals.ensure_fresh((size_t)ml * no * 8))
-                return rules_step_fail(h, SH_E_OOM, "event limiter buffers");
-            const bool hv = h->hv_on;
-            const shq_table T = carry_table(rate_tab(h));
-            if (rate_limit(h, ml, no, (hv ? h->hv_seq : h->w_oseq).as<uint64_t>(),
-                           (hv ? h->hv_vals : h->w_ovals).as<int64_t>(), (hv ? h->hv_q : h->rc_oq).as<int32_t>(),
-                           (hv ? h->hv_ts : h->rc_ots).as<int64_t>(),
-                           rl_keyed ? (hv ? h->hv_key : h->rc_okey).as<int32_t>() : nullptr, nullptr, nkeys, &T,
-                           h->rl_seq.as<uint64_t>(), h->rl_vals.as<int64_t>(), h->rl_q.as<int32_t>(),
-                           h->rl_ts.as<int64_t>(), &rl_pk, &rl_fin))
-                return rules_step_fail(h, SH_E_HIP, h->err.c_str());
-            unsigned long long kept = 0;
-            hipMemcpyAsync(&kept, h->rl_kept.p, 8, hipMemcpyDeviceToHost, st);
-            if (hipStreamSynchronize(st) != hipSuccess || (int64_t)kept > ml)
-                return rules_step_fail(h, SH_E_HIP, "device error in the event limiters");
-            mk = (int64_t)kept;
-        }
+        // `having`, then the event limiters on the rows it kept, from each run's carried
+        // counter: the rows handed to the host queue are the last pass's, from its own
+        // buffers (the limiters key the kept rows, so their keys move with them; the
+        // aggregates' table below takes every row's state, and the counters' moves last)
+        post.step = true;
+        post.src = shw_rows{h->w_oseq.as<uint64_t>(), h->w_ovals.as<int64_t>(), h->rc_oq.as<int32_t>(),
+                            h->rc_ots.as<int64_t>(), nullptr, rl_keyed ? h->rc_okey.as<int32_t>() : nullptr};
+        post.m = m;
+        post.n_out = no;
+        post.mid = &h->hv;
+        post.n_keys = nkeys;
+        post.tab = &h->rl_tab;
+        const int xrc = row_post(h, post);
+        if (xrc) return xrc;
+        ml = post.after_having;
+        mk = post.after_rate;
     } else {
         hipEventRecord(h->ev[2], st);
     }
@@ -958,49 +991,40 @@ int rules_step(sh_handle* h) {
     // rows into the host output queue; the per-key last timestamps move last, when
     // nothing can refuse the step any more
     const size_t base = h->o_seq.size();
-    h->o_query.resize(base + mk);
-    h->o_seq.resize(base + mk);
-    h->o_ts.resize(base + mk);
-    h->o_vals.resize((base + mk) * h->n_out);
-    h->o_nulls.resize((base + mk) * h->n_out, 0);
+    out_queue_rows(h, base + mk);
     if (mk > 0) {
-        const DevBuf& oq = h->rl_on ? h->rl_q : h->hv_on ? h->hv_q : h->rc_oq;
-        const DevBuf& oseq = h->rl_on ? h->rl_seq : h->hv_on ? h->hv_seq : h->w_oseq;
-        const DevBuf& ots = h->rl_on ? h->rl_ts : h->hv_on ? h->hv_ts : h->rc_ots;
-        const DevBuf& ovals = h->rl_on ? h->rl_vals : h->hv_on ? h->hv_vals : h->w_ovals;
-        hipMemcpyAsync(h->o_query.data() + base, oq.p, (size_t)mk * 4, hipMemcpyDeviceToHost, st);
-        hipMemcpyAsync(h->o_seq.data() + base, oseq.p, (size_t)mk * 8, hipMemcpyDeviceToHost, st);
-        hipMemcpyAsync(h->o_ts.data() + base, ots.p, (size_t)mk * 8, hipMemcpyDeviceToHost, st);
+        const shw_rows& o = post.out;
+        hipMemcpyAsync(h->o_query.data() + base, o.query, (size_t)mk * 4, hipMemcpyDeviceToHost, st);
+        hipMemcpyAsync(h->o_seq.data() + base, o.seq, (size_t)mk * 8, hipMemcpyDeviceToHost, st);
+        hipMemcpyAsync(h->o_ts.data() + base, o.ts, (size_t)mk * 8, hipMemcpyDeviceToHost, st);
         if (h->n_out)
-            hipMemcpyAsync(h->o_vals.data() + base * h->n_out, ovals.p, (size_t)mk * h->n_out * 8,
+            hipMemcpyAsync(h->o_vals.data() + base * h->n_out, o.vals, (size_t)mk * h->n_out * 8,
                            hipMemcpyDeviceToHost, st);
     }
     // ... and with them the segments' final aggregate states into their table
     uint64_t ag_ctl[2] = {0, 0};  // entries, error word
     int arc = 0;
     if (ag_pk) {
-        const shq_table T = agg_carry_table(h);
+        const shq_table T = carry_table(h->ag_tab);
         // (the device counter counts this launch alone: every shc_put starts it from zero)
-        hipMemsetAsync(h->ag_ctl.p, 0, 16, st);
-        arc = shc_put(&T, ag_pk, ag_fin, m, h->ag_ctl.as<unsigned long long>(), h->ag_ctl.as<int32_t>() + 2, st);
-        hipMemcpyAsync(ag_ctl, h->ag_ctl.p, 16, hipMemcpyDeviceToHost, st);
+        const DevBuf& ctl = h->ag_tab.ctl;
+        hipMemsetAsync(ctl.p, 0, 16, st);
+        arc = shc_put(&T, ag_pk, ag_fin, m, ctl.as<unsigned long long>(), ctl.as<int32_t>() + 2, st);
+        hipMemcpyAsync(ag_ctl, ctl.p, 16, hipMemcpyDeviceToHost, st);
     }
     // ... and the limiters' next counters into theirs
     uint64_t rl_ctl[2] = {0, 0};
-    if (rl_pk && !arc) {
-        const shq_table T = carry_table(rate_tab(h));
-        hipMemsetAsync(h->rl_ctl.p, 0, 16, st);
-        arc = shc_put(&T, rl_pk, rl_fin, ml, h->rl_ctl.as<unsigned long long>(), h->rl_ctl.as<int32_t>() + 2, st);
-        hipMemcpyAsync(rl_ctl, h->rl_ctl.p, 16, hipMemcpyDeviceToHost, st);
+    if (post.put_keys && !arc) {
+        const shq_table T = carry_table(h->rl_tab);
+        const DevBuf& ctl = h->rl_tab.ctl;
+        hipMemsetAsync(ctl.p, 0, 16, st);
+        arc = shc_put(&T, post.put_keys, post.put_state, ml, ctl.as<unsigned long long>(), ctl.as<int32_t>() + 2, st);
+        hipMemcpyAsync(rl_ctl, ctl.p, 16, hipMemcpyDeviceToHost, st);
     }
     if (shr_klast_update(sts, skeys, perm, n, (uint32_t)nc, h->rc_klast.as<int64_t>(), st) || arc ||
         (hipEventRecord(h->ev[3], st), hipStreamSynchronize(st)) != hipSuccess || (ag_ctl[1] & 1) ||
         (rl_ctl[1] & 1)) {
-        h->o_query.resize(base);
-        h->o_seq.resize(base);
-        h->o_ts.resize(base);
-        h->o_vals.resize(base * h->n_out);
-        h->o_nulls.resize(base * h->n_out);
+        out_queue_rows(h, base);
         return rules_step_fail(h, SH_E_HIP, "device error in the rule step");
     }
     phase_times(h);
@@ -1009,23 +1033,16 @@ int rules_step(sh_handle* h) {
     h->rc_pairs = npairs;
     h->rc_steps++;
     h->rs_last = 0;
-    if (ag_pk) h->ag_entries += (int64_t)ag_ctl[0];  // the slots this step claimed
+    if (ag_pk) h->ag_tab.entries += (int64_t)ag_ctl[0];  // the slots this step claimed
     if (h->r_aggp) h->agg_last = 6;
-    h->hv_last = h->hv_on ? 1 : 0;
-    h->hv_rows_in = m;
-    h->hv_rows_kept = ml;
-    if (rl_pk) h->rl_entries += (int64_t)rl_ctl[0];
-    h->rl_last = h->rl_on ? 1 : 0;
-    h->rl_rows_in = ml;
-    h->rl_rows_kept = mk;
-    h->rq_ts.clear();
-    h->rq_key.clear();
-    h->rq_seq.clear();
-    h->rq_run.clear();
-    for (auto& c : h->rq_col) c.clear();
-    h->rq_run_next = 0;
-    h->seq_staged0 = h->seq_next;
-    h->rq_call0 = h->rq_call;
+    h->hv.last = h->hv_on ? 1 : 0;
+    h->hv.rows_in = m;
+    h->hv.rows_kept = ml;
+    if (post.put_keys) h->rl_tab.entries += (int64_t)rl_ctl[0];
+    h->rl.last = h->rl_on ? 1 : 0;
+    h->rl.rows_in = ml;
+    h->rl.rows_kept = mk;
+    rules_unstage(h);
     return SH_OK;
 }
 

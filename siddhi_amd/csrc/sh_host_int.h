@@ -117,6 +117,49 @@ struct PinBuf {
 using shh::DevBuf;
 using shh::PinBuf;
 
+// What one pass of the row post-filter stage (`having`, the event limiters) owns on the
+// handle: its workspace, the kept count (8 bytes), destination buffers for the rows it
+// keeps, and the last run's or step's outcome
+struct RowStage {
+    DevBuf ws, kept, seq, q, ts, vals, key;
+    int last = 0;  // 1: the device pass ran in the last run or step
+    int64_t rows_in = 0, rows_kept = 0;
+    hipEvent_t ev[2] = {};  // around the pass's launches (made by the first one)
+    void release() {
+        for (DevBuf* b : {&ws, &kept, &seq, &q, &ts, &vals, &key}) b->release();
+        for (auto& e : ev) {
+            if (e) hipEventDestroy(e);
+            e = nullptr;
+        }
+    }
+    // the last run's or step's rows in and rows kept (0, 0 when the pass did not run)
+    int rows(int64_t* in, int64_t* out) const {
+        if (in) *in = last ? rows_in : 0;
+        if (out) *out = last ? rows_kept : 0;
+        return last;
+    }
+    // device time of the last run's or step's launches, ms
+    double ms() const {
+        float t = 0.f;
+        return last && ev[1] && hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess ? t : 0.0;
+    }
+};
+
+// A carried-state table (sh_agg.hip shc_*: the aggregates' states, the limiters'
+// counters): open addressing, kept at most half full; ctl: the slots one k_shc_put
+// launch claimed (8 bytes, zeroed before every launch; entries is the host's sum of
+// them) and its error word
+struct CarryTab {
+    DevBuf keys, state, ctl;
+    int64_t cap = 0, entries = 0;
+    int32_t ncols = 0;
+    void release() {
+        for (DevBuf* b : {&keys, &state, &ctl}) b->release();
+        cap = entries = 0;
+        ncols = 0;
+    }
+};
+
 #define SH_HP_N 12
 // one k_nfa_run launch of the general engine: what its completion and any replay
 // need (sh_host_nfa.cpp nf_launch / nf_complete); a streaming push leaves it
@@ -345,13 +388,9 @@ struct sh_handle {
     int64_t* step_ots = nullptr;         // ... and where the rows' timestamps go
     int32_t* step_okey = nullptr;        // ... and the partition keys of their consuming events
     // carried aggregates of an aggregating set (sh_agg.hip shc_*): per (query, key)
-    // that ever produced a row, per aggregate column, the running sum and count, in
-    // an open-addressing table kept at most half full; ag_ctl: the slots one
-    // k_shc_put launch claimed (8 bytes, zeroed before every launch; ag_entries is
-    // the host's sum of them) and its error word
-    DevBuf ag_keys, ag_state, ag_ctl, rc_okey;
-    int64_t ag_cap = 0, ag_entries = 0;
-    int32_t ag_ncols = 0;
+    // that ever produced a row, per aggregate column, the running sum and count
+    CarryTab ag_tab;
+    DevBuf rc_okey;
     // ---- bucketed window engine (sh_bucket.hip + shb_match): 0 untried, 1 loaded, <0 unavailable
     int bk_state = 0;
     int32_t part_attr0 = -1;  // stream-0 attribute keying query 0's partition
@@ -385,31 +424,24 @@ struct sh_handle {
                        // 6: carried sequential pass (k_shc_walk: a rule set beyond the general engine's table)
     // ---- output-only `having` behind the fast engines (sh_having.h / sh_having.hip):
     // one row predicate per query (an empty program keeps every row), the device
-    // copy, the filter's workspace and its destination buffers (a streaming step
-    // hands the host queue the kept rows from them), and the last run's counts
+    // copy, and the pass's record (a streaming step hands the host queue the kept rows
+    // from its buffers)
     bool hv_on = false;
     bool hv_chain = false;             // a one-query window-shaped app (with a `having` or an event limiter):
                                        // mode 1 to stream, the chain rungs in bulk
     std::vector<shv_prog> hv_progs;
-    DevBuf hv_d_progs, hv_ws, hv_kept, hv_seq, hv_q, hv_ts, hv_vals, hv_key;
-    int hv_last = 0;                   // 1: the device row filter ran in the last run or step
-    int64_t hv_rows_in = 0, hv_rows_kept = 0;
-    hipEvent_t hv_ev[2] = {};          // around the filter's launches (made by the first one)
+    DevBuf hv_d_progs;
+    RowStage hv;
     // ---- `output first|last every N events` behind the fast engines (sh_rate.h /
     // sh_rate.hip): one rule per query (SH_RATE_NONE keeps every row), the device copy,
-    // the pass's workspace and its destination buffers (as the filter's above), the
-    // last run's counts, and -- for a streaming rule set -- the carried counter of
+    // the pass's record, and -- for a streaming rule set -- the carried counter of
     // every (query, key) that ever reached a limiter, in a one-column table of the
     // aggregates' kind (state[slot * 2]: the reduced counter of sh_rate.h)
     bool rl_on = false;
     std::vector<shl_rule> rl_rules;
-    DevBuf rl_d_rules, rl_ws, rl_kept, rl_seq, rl_q, rl_ts, rl_vals;
-    int rl_last = 0;                   // 1: the device pass ran in the last run or step
-    int64_t rl_rows_in = 0, rl_rows_kept = 0;
-    hipEvent_t rl_ev[2] = {};
-    DevBuf rl_keys, rl_state, rl_ctl;
-    int64_t rl_cap = 0, rl_entries = 0;
-    int32_t rl_ncols = 0;
+    DevBuf rl_d_rules;
+    RowStage rl;
+    CarryTab rl_tab;
     std::vector<int32_t> out_types;  // per select position over the queries (-2: types differ)
     uint64_t fp = 0;                 // compiled-program fingerprint (snapshot images)
 };
@@ -475,20 +507,11 @@ int nf_upload_table(sh_handle* h);
 int agg_post(sh_handle* h, sh_device_run* run, int32_t nkeys, const int32_t* d_query, int n_query,
              const int32_t* agg_kind, const int32_t* arg_type, int n_out);
 int agg_carry_cols(const sh_handle* h);
-// a carried-state table of the handle (the aggregates' or the limiters' counters)
-struct CarryTab {
-    DevBuf &keys, &state, &ctl;
-    int64_t &cap, &entries;
-    int32_t& ncols;
-};
-inline CarryTab agg_tab(sh_handle* h) { return {h->ag_keys, h->ag_state, h->ag_ctl, h->ag_cap, h->ag_entries, h->ag_ncols}; }
-inline CarryTab rate_tab(sh_handle* h) { return {h->rl_keys, h->rl_state, h->rl_ctl, h->rl_cap, h->rl_entries, h->rl_ncols}; }
+// a carried-state table of the handle (h->ag_tab, h->rl_tab)
 shq_table carry_table(const CarryTab& C);
-int carry_reserve(sh_handle* h, const CarryTab& C, int64_t add, int n_cols);
+int carry_reserve(sh_handle* h, CarryTab& C, int64_t add, int n_cols);
 int carry_dump(const CarryTab& C, std::vector<uint64_t>& keys, std::vector<int64_t>& state);
-int carry_load(sh_handle* h, const CarryTab& C, int n_cols, const uint64_t* keys, const int64_t* state, int64_t n);
-int agg_carry_dump(sh_handle* h, std::vector<uint64_t>& keys, std::vector<int64_t>& state);
-int agg_carry_load(sh_handle* h, const uint64_t* keys, const int64_t* state, int64_t n);
+int carry_load(sh_handle* h, CarryTab& C, int n_cols, const uint64_t* keys, const int64_t* state, int64_t n);
 int bits_for(uint64_t v);
 int carry_setup(sh_handle* h, const sh_device_run* run, shd_payload* carry, void** mid, int* alias,
                 bool used_only = false, bool with_ts = true);
@@ -510,19 +533,43 @@ int run_window(sh_handle* h, sh_device_run* run, int32_t nkeys);
 int run_rules(sh_handle* h, sh_device_run* run);
 int rules_stage(sh_handle* h, const sh_batch* b);
 int rules_step(sh_handle* h);
-// the device row filter over m ordered rows (sources and destinations apart, query /
-// ts NULL where the path has none); the kept count lands in h->hv_kept (8 bytes)
-int having_filter(sh_handle* h, int64_t m, int n_out, const uint64_t* seq, const int64_t* vals, const int32_t* query,
-                  const int64_t* ts, uint64_t* o_seq, int64_t* o_vals, int32_t* o_query, int64_t* o_ts,
-                  const int32_t* key = nullptr, int32_t* o_key = nullptr);
+// the device row filter over the m ordered rows of src into dst (shw_rows, sh_having.h:
+// columns NULL where the path has none); the kept count lands in h->hv.kept (8 bytes)
+int having_filter(sh_handle* h, int64_t m, int n_out, const shw_rows& src, const shw_rows_out& dst);
 // the event limiters' pass (sh_rate.hip) over m ordered rows, as having_filter: keys
-// from rowkey, else keys[seq] (NULL, NULL: one key); T the carried counters (NULL:
-// every run from zero); the kept count lands in h->rl_kept, put_keys / put_state
+// from src.key, else keys[seq] (NULL, NULL: one key); T the carried counters (NULL:
+// every run from zero); the kept count lands in h->rl.kept, put_keys / put_state
 // take what shc_put carries
-int rate_limit(sh_handle* h, int64_t m, int n_out, const uint64_t* seq, const int64_t* vals, const int32_t* query,
-               const int64_t* ts, const int32_t* rowkey, const int32_t* keys, int32_t n_keys, const shq_table* T,
-               uint64_t* o_seq, int64_t* o_vals, int32_t* o_query, int64_t* o_ts, const uint64_t** put_keys,
-               const int64_t** put_state);
+int rate_limit(sh_handle* h, int64_t m, int n_out, const shw_rows& src, const int32_t* keys, int32_t n_keys,
+               const shq_table* T, const shw_rows_out& dst, const uint64_t** put_keys, const int64_t** put_state);
+// One run of the row post-filter stage behind an engine: `having` (h->hv_on), then the
+// event limiters (h->rl_on) on the rows it kept, each pass launched, its kept count
+// read back (8 bytes, one synchronise) and checked, and the next one's source
+// re-pointed at what it wrote. A pass that is the last writes `end`, or its own
+// buffers (h->hv / h->rl) when end is NULL; `having` ahead of the limiters writes
+// mid's buffers. Such a buffer set has `room` rows (0: the pass's input) and every
+// column the source has, the key only ahead of the limiters.
+struct RowPost {
+    bool step = false;  // a streaming step (rules_step): refusals go through its own
+                        // exit, limiters that no row reaches are skipped, and the
+                        // passes' records (last, rows) are left to the step's end
+    shw_rows src{};     // the engine's m rows
+    int64_t m = 0;
+    int n_out = 1;
+    const shw_rows_out* end = nullptr;
+    RowStage* mid = nullptr;
+    size_t room = 0;
+    const int32_t* d_keys = nullptr;  // the limiters' keys through d_keys[seq] (else src.key, else one key)
+    int32_t n_keys = 1;
+    CarryTab* tab = nullptr;  // the limiters' carried counters (NULL: every run from zero)
+    // what it answers: the rows `having` / the limiters left, where they are, and what
+    // shc_put takes to carry the limiters' counters (with a table)
+    int64_t after_having = 0, after_rate = 0;
+    shw_rows out{};
+    const uint64_t* put_keys = nullptr;
+    const int64_t* put_state = nullptr;
+};
+int row_post(sh_handle* h, RowPost& P);
 int run_s3b(sh_handle* h, sh_device_run* run, int32_t nkeys);
 shd_segment_ws seg_ws(sh_handle* h, int64_t n);
 int tile_shift_for(int64_t n, int32_t nkeys);

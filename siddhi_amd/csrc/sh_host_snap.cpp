@@ -208,7 +208,7 @@ static int snapshot_image(sh_handle* h, SnapW& w) {
             // each with its per-column (sum, count) -- equal states, equal images
             std::vector<uint64_t> ak;
             std::vector<int64_t> as;
-            if (agg_carry_dump(h, ak, as)) w.bad = true;
+            if (carry_dump(h->ag_tab, ak, as)) w.bad = true;
             w.put<int32_t>(agg_carry_cols(h));
             w.vec(ak);
             w.vec(as);
@@ -217,7 +217,7 @@ static int snapshot_image(sh_handle* h, SnapW& w) {
             // event limiters: the (query, key) runs sorted by table key, each with its counter
             std::vector<uint64_t> lk;
             std::vector<int64_t> ls;
-            if (carry_dump(rate_tab(h), lk, ls)) w.bad = true;
+            if (carry_dump(h->rl_tab, lk, ls)) w.bad = true;
             std::vector<uint32_t> lc(lk.size());
             for (size_t i = 0; i < lk.size(); i++) lc[i] = (uint32_t)ls[i * 2];
             w.vec(lk);
@@ -383,7 +383,7 @@ static int restore_image(sh_handle* h, const void* buf, int64_t size) {
             if (nc != agg_carry_cols(h) || as.size() != ak.size() * (size_t)nc * 2) r.bad = true;
             for (size_t i = 0; i < ak.size() && !r.bad; i++)
                 if (ak[i] == SHQ_EMPTY || (i && ak[i] <= ak[i - 1])) r.bad = true;
-            if (!r.bad && agg_carry_load(h, ak.data(), as.data(), (int64_t)ak.size())) r.bad = true;
+            if (!r.bad && carry_load(h, h->ag_tab, nc, ak.data(), as.data(), (int64_t)ak.size())) r.bad = true;
         }
         if (!r.bad && h->rl_on) {
             std::vector<uint64_t> lk;
@@ -400,7 +400,7 @@ static int restore_image(sh_handle* h, const void* buf, int64_t size) {
             }
             std::vector<int64_t> ls(lk.size() * 2, 0);
             for (size_t i = 0; i < lk.size(); i++) ls[i * 2] = (int64_t)lc[i];
-            if (!r.bad && carry_load(h, rate_tab(h), 1, lk.data(), ls.data(), (int64_t)lk.size())) r.bad = true;
+            if (!r.bad && carry_load(h, h->rl_tab, 1, lk.data(), ls.data(), (int64_t)lk.size())) r.bad = true;
         }
         if (r.bad) h->rc_rows = h->rc_pairs = h->rc_nkeys = 0;
     } else if (h->mode == 0 && !r.bad) {

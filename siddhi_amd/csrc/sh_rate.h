@@ -55,6 +55,8 @@ SHL_HD uint32_t shl_next(const shl_rule& R, uint32_t c0, uint64_t rows) {
 
 // ---- the device pass (sh_rate.hip), all launches asynchronous on `stream`
 struct shq_table;
+struct shw_rows;
+struct shw_rows_out;
 #define SHL_TILE 2048  // rows per scan tile
 
 #ifdef __cplusplus
@@ -62,20 +64,19 @@ extern "C" {
 #endif
 // 4-byte words of workspace for m rows (8-byte aligned by the caller)
 int64_t shl_limit_ws_words(int64_t m);
-// The m ordered raw rows (seq, vals [m x n_out], query / ts / nulls optional) through
-// their queries' limiters (rules[q], n_rules of them in HBM; query ids are in [0,
-// n_rules), a row without a query id is query 0's): the kept rows go, in
-// order, to the o_* buffers (apart from the sources), their count to *d_kept (8
-// bytes). A row's key is d_rowkey[r], else d_keys[seq[r] - seq_base], else 0; keys
-// are below n_keys. A run starts from its (query << 32 | key) entry of T (one column:
-// state[slot * 2] the counter; NULL or cap 0: from zero); T is only read. put_keys /
-// put_state (in ws, m entries; both NULL: not written): what shc_put takes to carry the
-// runs' counters (limited queries' runs only). 0: launched, < 0: error.
-int shl_limit(const shl_rule* rules, int32_t n_rules, int64_t m, int32_t n_out, const uint64_t* seq,
-              const int64_t* vals, const int32_t* query, const int64_t* ts, const uint8_t* nulls,
-              const int32_t* d_rowkey, const int32_t* d_keys, int32_t n_keys, uint64_t seq_base, const shq_table* T,
-              uint64_t* o_seq, int64_t* o_vals, int32_t* o_query, int64_t* o_ts, uint8_t* o_nulls, uint32_t* ws,
-              unsigned long long* d_kept, void* stream, const uint64_t** put_keys, const int64_t** put_state);
+// The m ordered raw rows of src (shw_rows, sh_having.h) through their queries'
+// limiters (rules[q], n_rules of them in HBM; query ids are in [0, n_rules), a row
+// without a query id is query 0's): the kept rows go, in order, to dst, their count
+// to *d_kept (8 bytes). A row's key is src->key[r], else d_keys[seq[r] - seq_base],
+// else 0; keys are below n_keys. A run starts from its (query << 32 | key) entry of T
+// (one column: state[slot * 2] the counter; NULL or cap 0: from zero); T is only
+// read. put_keys / put_state (in ws, m entries; both NULL: not written): what shc_put
+// takes to carry the runs' counters (limited queries' runs only). 0: launched, < 0:
+// error.
+int shl_limit(const shl_rule* rules, int32_t n_rules, int64_t m, int32_t n_out, const struct shw_rows* src,
+              const int32_t* d_keys, int32_t n_keys, uint64_t seq_base, const shq_table* T,
+              const struct shw_rows_out* dst, uint32_t* ws, unsigned long long* d_kept, void* stream,
+              const uint64_t** put_keys, const int64_t** put_state);
 #ifdef __cplusplus
 }
 #endif

@@ -273,11 +273,9 @@ int shl_ok() { return hipGetLastError() == hipSuccess ? 0 : -3; }
 
 extern "C" int64_t shl_limit_ws_words(int64_t m) { return shl_layout(m > 0 ? m : 1, nullptr).bytes / 4; }
 
-extern "C" int shl_limit(const shl_rule* rules, int32_t n_rules, int64_t m, int32_t n_out, const uint64_t* seq,
-                         const int64_t* vals, const int32_t* query, const int64_t* ts, const uint8_t* nulls,
-                         const int32_t* d_rowkey, const int32_t* d_keys, int32_t n_keys, uint64_t seq_base,
-                         const shq_table* T, uint64_t* o_seq, int64_t* o_vals, int32_t* o_query, int64_t* o_ts,
-                         uint8_t* o_nulls, uint32_t* ws, unsigned long long* d_kept, void* stream,
+extern "C" int shl_limit(const shl_rule* rules, int32_t n_rules, int64_t m, int32_t n_out, const shw_rows* src,
+                         const int32_t* d_keys, int32_t n_keys, uint64_t seq_base, const shq_table* T,
+                         const shw_rows_out* dst, uint32_t* ws, unsigned long long* d_kept, void* stream,
                          const uint64_t** put_keys, const int64_t** put_state) {
     hipStream_t st = (hipStream_t)stream;
     if (put_keys) *put_keys = nullptr;
@@ -285,9 +283,13 @@ extern "C" int shl_limit(const shl_rule* rules, int32_t n_rules, int64_t m, int3
     if (!d_kept || m < 0 || m >= 0x7FFFFFFFll || n_out < 1 || n_out > SHV_MAX_OUT || n_rules < 1 || !rules) return -1;
     if (T && T->cap > 0 && ((T->cap & (T->cap - 1)) || T->n_cols != 1 || !T->keys || !T->state)) return -1;
     if (m == 0) return hipMemsetAsync(d_kept, 0, 8, st) == hipSuccess ? 0 : -3;
-    if (!vals || !o_vals || !ws || (o_seq && !seq) || (o_query && !query) || (o_ts && !ts) || (o_nulls && !nulls) ||
-        (!d_rowkey && d_keys && !seq) || ((uintptr_t)ws & 7))
+    if (!src || !dst || !src->vals || !dst->vals || !ws || (dst->seq && !src->seq) || (dst->query && !src->query) ||
+        (dst->ts && !src->ts) || (dst->nulls && !src->nulls) || (dst->key && !src->key) ||
+        (!src->key && d_keys && !src->seq) || ((uintptr_t)ws & 7))
         return -1;
+    const uint64_t* seq = src->seq;
+    const int32_t* query = src->query;
+    const int32_t* d_rowkey = src->key;
     const shl_ws W = shl_layout(m, (uint8_t*)ws);
     const unsigned g = (unsigned)((m + SHL_TPB - 1) / SHL_TPB);
     const int64_t nt = (m + SHL_TILE - 1) / SHL_TILE, vt = (m + SHV_TILE - 1) / SHV_TILE;
@@ -331,9 +333,7 @@ extern "C" int shl_limit(const shl_rule* rules, int32_t n_rules, int64_t m, int3
     hipLaunchKernelGGL(k_shl_mark, dim3((unsigned)vt), dim3(SHV_TILE), 0, st, (const uint8_t*)W.keepb, m, W.mask,
                        W.cnt);
     if (shl_ok()) return -3;
-    if (shv_move_marked(m, n_out, seq, vals, query, ts, nulls, o_seq, o_vals, o_query, o_ts, o_nulls, W.mask, W.cnt,
-                        W.off, W.tmp, d_kept, stream))
-        return -3;
+    if (shv_move_marked(m, n_out, src, dst, W.mask, W.cnt, W.off, W.tmp, d_kept, stream)) return -3;
     if (put) {
         *put_keys = W.pk;
         *put_state = W.fin;

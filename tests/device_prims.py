@@ -5,8 +5,9 @@ sh_window.hip, called through ctypes with torch device pointers and compared wit
 numpy restatements of what siddhi_amd/csrc/sh_device.h promises.
 
 Held fixed here:
-  * the ctypes mirrors of shd_batch / shd_segment_ws / shd_payload (checked against
-    the header by tests/prims_layout);
+  * the ctypes mirrors of shd_batch / shd_segment_ws / shd_payload, and of the row
+    sets shw_rows / shw_rows_out of sh_having.h (checked against the headers by
+    tests/prims_layout);
   * the numpy contracts (*_ref), written from the header comments, not the kernels;
   * the workspace sizes in 4-byte words as the header and the callers state them.
     Every device buffer has exactly that size plus a guard of GUARD words; outputs
@@ -48,7 +49,18 @@ class shd_payload(C.Structure):
                 ("width", C.c_uint8 * 8)]
 
 
-MIRRORS = {"shd_batch": shd_batch, "shd_segment_ws": shd_segment_ws, "shd_payload": shd_payload}
+class shw_rows(C.Structure):
+    """a set of rows as parallel columns (sh_having.h); shw_rows_out is its writable twin"""
+    _fields_ = [("seq", C.c_void_p), ("vals", C.c_void_p), ("query", C.c_void_p), ("ts", C.c_void_p),
+                ("nulls", C.c_void_p), ("key", C.c_void_p)]
+
+
+class shw_rows_out(C.Structure):
+    _fields_ = list(shw_rows._fields_)
+
+
+MIRRORS = {"shd_batch": shd_batch, "shd_segment_ws": shd_segment_ws, "shd_payload": shd_payload,
+           "shw_rows": shw_rows, "shw_rows_out": shw_rows_out}
 
 _lib = None
 

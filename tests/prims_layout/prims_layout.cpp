@@ -5,6 +5,7 @@
 #include <stdio.h>
 
 #include "../../siddhi_amd/csrc/sh_device.h"
+#include "../../siddhi_amd/csrc/sh_having.h"
 
 #define SZ(S) printf(#S " sizeof %zu\n", sizeof(S))
 #define OFF(S, M) printf(#S " " #M " %zu\n", offsetof(S, M))
@@ -34,5 +35,19 @@ int main() {
     OFF(shd_payload, src);
     OFF(shd_payload, dst);
     OFF(shd_payload, width);
+    SZ(shw_rows);
+    OFF(shw_rows, seq);
+    OFF(shw_rows, vals);
+    OFF(shw_rows, query);
+    OFF(shw_rows, ts);
+    OFF(shw_rows, nulls);
+    OFF(shw_rows, key);
+    SZ(shw_rows_out);
+    OFF(shw_rows_out, seq);
+    OFF(shw_rows_out, vals);
+    OFF(shw_rows_out, query);
+    OFF(shw_rows_out, ts);
+    OFF(shw_rows_out, nulls);
+    OFF(shw_rows_out, key);
     return 0;
 }

@@ -9,6 +9,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from device_prims import shw_rows, shw_rows_out
 from having_fast_cases import (AGGREGATING, BY_NAME, H1, H2, INSERT, PLAIN, assert_all_rows_equal, having_ref,
                                with_having)
 from oracle_engine import OracleEngine, run_columns_oracle
@@ -309,9 +310,15 @@ def _prim_lib():
     vp = C.c_void_p
     L.shv_filter_ws_words.argtypes = [C.c_int64]
     L.shv_filter_ws_words.restype = C.c_int64
-    L.shv_filter.argtypes = [vp, C.c_int32, C.c_int64, C.c_int32] + [vp] * 13
+    L.shv_filter.argtypes = [vp, C.c_int32, C.c_int64, C.c_int32, C.POINTER(shw_rows), C.POINTER(shw_rows_out),
+                             vp, vp, vp]
     L.shv_filter.restype = C.c_int
     return L
+
+
+def _ptrs(cls, **cols):
+    """a row set from device tensors (a column left out, or None, is NULL)"""
+    return cls(**{k: t.data_ptr() for k, t in cols.items() if t is not None})
 
 
 M_TILES = [1, 63, 64, 65, TILE - 1, TILE, TILE + 1, 3 * TILE + 17, (SCAN_TILE + 2) * TILE + 5]
@@ -366,16 +373,19 @@ def test_filter_primitive_vs_numpy(m, n_out, extras):
         def to_dev(a):
             return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
 
+        key = rng.integers(-(1 << 31), 1 << 31, m).astype(np.int32)
         d_seq, d_vals = to_dev(seq.view(np.int64)), to_dev(vals)
-        d_q, d_ts, d_nulls = to_dev(query), to_dev(ts), to_dev(nulls)
+        d_q, d_ts, d_nulls, d_key = to_dev(query), to_dev(ts), to_dev(nulls), to_dev(key)
         o_seq, o_vals = guarded(m * 8), guarded(m * n_out * 8)
-        o_q, o_ts, o_nulls = guarded(m * 4), guarded(m * 8), guarded(m * n_out)
+        o_q, o_ts, o_nulls, o_key = guarded(m * 4), guarded(m * 8), guarded(m * n_out), guarded(m * 4)
         ws, kept = guarded(ws_words * 4), guarded(8)
-        rc = L.shv_filter(d_prog.data_ptr(), 2, m, n_out, d_seq.data_ptr(), d_vals.data_ptr(),
-                          d_q.data_ptr() if extras else None, d_ts.data_ptr() if extras else None,
-                          d_nulls.data_ptr() if extras else None, o_seq.data_ptr(), o_vals.data_ptr(),
-                          o_q.data_ptr() if extras else None, o_ts.data_ptr() if extras else None,
-                          o_nulls.data_ptr() if extras else None, ws.data_ptr(), kept.data_ptr(),
+        # (without the extras the optional columns are NULL on both sides: a NULL
+        # destination never asks for its source)
+        src = _ptrs(shw_rows, seq=d_seq, vals=d_vals, **(dict(query=d_q, ts=d_ts, nulls=d_nulls, key=d_key)
+                                                          if extras else {}))
+        dst = _ptrs(shw_rows_out, seq=o_seq, vals=o_vals, **(dict(query=o_q, ts=o_ts, nulls=o_nulls, key=o_key)
+                                                              if extras else {}))
+        rc = L.shv_filter(d_prog.data_ptr(), 2, m, n_out, C.byref(src), C.byref(dst), ws.data_ptr(), kept.data_ptr(),
                           torch.cuda.current_stream(dev).cuda_stream)
         assert rc == 0
         torch.cuda.synchronize()
@@ -395,12 +405,43 @@ def test_filter_primitive_vs_numpy(m, n_out, extras):
         assert np.all(out(o_vals, m * n_out * 8, np.uint8)[k * n_out * 8:] == FILL)
         got_q, got_ts = out(o_q, m * 4, np.int32), out(o_ts, m * 8, np.int64)
         got_nulls = out(o_nulls, m * n_out, np.uint8).reshape(m, n_out)
+        got_key = out(o_key, m * 4, np.int32)
         if extras:
             assert np.array_equal(got_q[:k], query[keep]) and np.array_equal(got_ts[:k], ts[keep])
             assert np.array_equal(got_nulls[:k], nulls[keep])
+            assert np.array_equal(got_key[:k], key[keep]), pattern
+            assert np.all(out(o_key, m * 4, np.uint8)[k * 4:] == FILL)
         else:
             assert np.all(out(o_q, m * 4, np.uint8) == FILL) and np.all(out(o_ts, m * 8, np.uint8) == FILL)
             assert np.all(out(o_nulls, m * n_out, np.uint8) == FILL)
+            assert np.all(out(o_key, m * 4, np.uint8) == FILL)
+
+
+@pytest.mark.parametrize("col", ["key", "ts"])
+def test_filter_primitive_refuses_a_destination_without_its_source(col):
+    """dst.key (dst.ts) set while src.key (src.ts) is NULL: -1, nothing launched --
+    every output, the workspace and the kept word stay as filled"""
+    import torch
+    L = _prim_lib()
+    dev = torch.device("cuda:0")
+    m, n_out = TILE + 1, 2
+    P = (shv_prog * 1)(_greater_than(-1))   # (would keep every row)
+    d_prog = torch.from_numpy(np.frombuffer(bytes(P), np.uint8).copy()).to(dev)
+    ws_words = L.shv_filter_ws_words(m)
+
+    def guarded(nbytes):
+        return torch.full((nbytes + 4 * GUARD,), FILL, dtype=torch.uint8, device=dev)
+
+    d_vals = torch.arange(m * n_out, dtype=torch.int64, device=dev)
+    o_vals, o_col, ws, kept = guarded(m * n_out * 8), guarded(m * 8), guarded(ws_words * 4), guarded(8)
+    src = _ptrs(shw_rows, vals=d_vals)
+    dst = _ptrs(shw_rows_out, vals=o_vals, **{col: o_col})
+    rc = L.shv_filter(d_prog.data_ptr(), 1, m, n_out, C.byref(src), C.byref(dst), ws.data_ptr(), kept.data_ptr(),
+                      torch.cuda.current_stream(dev).cuda_stream)
+    assert rc == -1
+    torch.cuda.synchronize()
+    for t in (o_vals, o_col, ws, kept):
+        assert bool((t == FILL).all()), col
 
 
 def test_filter_primitive_zero_rows():
@@ -410,7 +451,7 @@ def test_filter_primitive_zero_rows():
     P = (shv_prog * 1)(_greater_than(0))
     d_prog = torch.from_numpy(np.frombuffer(bytes(P), np.uint8).copy()).to(dev)
     kept = torch.full((8 + 4 * GUARD,), FILL, dtype=torch.uint8, device=dev)
-    rc = L.shv_filter(d_prog.data_ptr(), 1, 0, 1, *([None] * 11), kept.data_ptr(),
+    rc = L.shv_filter(d_prog.data_ptr(), 1, 0, 1, None, None, None, kept.data_ptr(),
                       torch.cuda.current_stream(dev).cuda_stream)
     assert rc == 0
     torch.cuda.synchronize()

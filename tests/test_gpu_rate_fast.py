@@ -10,6 +10,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from device_prims import shw_rows, shw_rows_out
 from having_fast_cases import PLAIN, assert_all_rows_equal
 from oracle_engine import OracleEngine, run_columns_oracle
 from rate_fast_cases import AGGREGATING, BY_NAME, R_F3, mix, rate_ref, with_rate
@@ -323,8 +324,8 @@ def _prim_lib():
     vp = C.c_void_p
     L.shl_limit_ws_words.argtypes = [C.c_int64]
     L.shl_limit_ws_words.restype = C.c_int64
-    L.shl_limit.argtypes = ([vp, C.c_int32, C.c_int64, C.c_int32] + [vp] * 7 + [C.c_int32, C.c_uint64, vp] + [vp] * 8 +
-                            [C.POINTER(vp), C.POINTER(vp)])
+    L.shl_limit.argtypes = [vp, C.c_int32, C.c_int64, C.c_int32, C.POINTER(shw_rows), vp, C.c_int32, C.c_uint64, vp,
+                            C.POINTER(shw_rows_out), vp, vp, vp, C.POINTER(vp), C.POINTER(vp)]
     L.shl_limit.restype = C.c_int
     L.shc_put.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp]
     L.shc_put.restype = C.c_int
@@ -441,12 +442,12 @@ def _run_pass(L, dev, rules, query, key, n_keys, n_out, carried, table, via_seq,
                          ctl.data_ptr() + 8, stream) == 0
         keep_alive += [tk, tst, ctl, d_pk, d_fin]
     put_k, put_s = C.c_void_p(), C.c_void_p()
-    rc = L.shl_limit(d_rules.data_ptr(), len(rules), m, n_out, d_seq.data_ptr(), d_vals.data_ptr(), d_q.data_ptr(),
-                     d_ts.data_ptr(), d_nulls.data_ptr(), None if via_seq else d_key.data_ptr(),
-                     d_key.data_ptr() if via_seq else None, n_keys, seq_base if via_seq else 0,
-                     C.byref(tab) if tab is not None else None, o_seq.data_ptr(), o_vals.data_ptr(), o_q.data_ptr(),
-                     o_ts.data_ptr(), o_nulls.data_ptr(), ws.data_ptr(), kept.data_ptr(), stream, C.byref(put_k),
-                     C.byref(put_s))
+    src = shw_rows(d_seq.data_ptr(), d_vals.data_ptr(), d_q.data_ptr(), d_ts.data_ptr(), d_nulls.data_ptr(),
+                   None if via_seq else d_key.data_ptr())
+    dst = shw_rows_out(o_seq.data_ptr(), o_vals.data_ptr(), o_q.data_ptr(), o_ts.data_ptr(), o_nulls.data_ptr(), None)
+    rc = L.shl_limit(d_rules.data_ptr(), len(rules), m, n_out, C.byref(src), d_key.data_ptr() if via_seq else None,
+                     n_keys, seq_base if via_seq else 0, C.byref(tab) if tab is not None else None, C.byref(dst),
+                     ws.data_ptr(), kept.data_ptr(), stream, C.byref(put_k), C.byref(put_s))
     assert rc == 0
     torch.cuda.synchronize()
     if table == "filled":
