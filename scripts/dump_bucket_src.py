@@ -1,6 +1,8 @@
 """Write the generated bucketed-matcher source (shb_match + shb_pmatch) of an app
-(default C2) to a file and print each kernel's register / LDS / scratch use, from
-an offline hipcc build of that source (no GPU needed)."""
+(default C2) to a file, and the generated source of its specialised emitter in the
+packed layout beside it (<file>.emit.hip), and print each kernel's register / LDS /
+scratch use, from offline hipcc builds of those sources (no GPU needed).
+scripts/emit_spec_resources.py compiles the emitter's other forms."""
 import ctypes as C
 import os
 import re
@@ -19,8 +21,17 @@ def main(out="/tmp/shb_src.hip", app=synth.C2_QUERY):
     buf = C.create_string_buffer(1 << 22)
     rc = lib.shx_bucket_compile(h, buf, 1 << 22)
     src = buf.value.decode()
+    erc = lib.shx_emit_compile(h, 2, buf, 1 << 22)  # SHB_OUT_PACKED
+    emit_src = buf.value.decode() if erc == abi.SH_OK else None
     lib.sh_destroy(h)
     assert rc == abi.SH_OK, rc
+    rc = resources(src, out)
+    if emit_src is not None:
+        rc = resources(emit_src, out + ".emit.hip") or rc
+    return rc
+
+
+def resources(src, out):
     # hipcc form: the hipRTC prelude's typedefs come from the HIP headers instead
     body = re.sub(r"^typedef __hip_internal::.*$|^typedef decltype\(sizeof\(0\)\) size_t;$|^#define INT(32|64)_MIN .*$",
                   "", src, flags=re.M)

@@ -170,6 +170,12 @@ def bind_product(lib):
     lib.shx_bucket_compile.restype = C.c_int
     lib.shx_bucket_status.argtypes = [C.c_void_p]
     lib.shx_bucket_status.restype = C.c_int
+    lib.shx_bucket_emit_status.argtypes = [C.c_void_p]
+    lib.shx_bucket_emit_status.restype = C.c_int
+    lib.shx_emit_compile.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_int64]
+    lib.shx_emit_compile.restype = C.c_int
+    lib.shx_emit_compile_key.argtypes = [C.POINTER(C.c_int32), C.c_char_p, C.c_int64, C.c_char_p, C.c_int64]
+    lib.shx_emit_compile_key.restype = C.c_int
     lib.shx_seq3_status.argtypes = [C.c_void_p]
     lib.shx_seq3_status.restype = C.c_int
     lib.shx_agg_status.argtypes = [C.c_void_p]

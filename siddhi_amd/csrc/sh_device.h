@@ -251,6 +251,9 @@ int shb_s3_carry(const shb_plan* P, const shb_s3* S, void* stream);
 int shb_agg_carry(const shb_plan* P, const shb_aggc* A, void* stream);
 int shb_emit(const shb_plan* P, const shb_out* O, const shb_cols* OC, uint64_t seq_base, uint64_t* out_seq,
              int64_t* out_vals, int64_t out_cap, void* stream);
+// shb_emit through a kernel compiled for the select list and layout (fn: hipFunction_t, sh_jit.h shj_emit_load)
+int shb_emit_spec(void* fn, const shb_plan* P, const shb_out* O, const shb_cols* OC, uint64_t seq_base,
+                  uint64_t* out_seq, int64_t* out_vals, int64_t out_cap, void* stream);
 // raw 8-byte rows [m x n_out] -> typed columns of widths w[o] (8, 4 or 1 bytes)
 int shd_narrow_rows(const int64_t* vals, int32_t n_out, int64_t m, void* const* cols, const int32_t* w, void* stream);
 // raw rows + sequence numbers -> packed rows (SHB_OUT_PACKED; woff / rw as in shb_cols)

@@ -1865,6 +1865,17 @@ int shx_bucket_status(sh_handle* h) {
     return h->bk_last;
 }
 
+// the emitter launched by the last sh_run_device that reached the bucketed or the
+// sequence bucket-carry engine (also when the rows then did not fit the capacity):
+// 1 the kernel compiled for its select list and layout, 0 the generic k_bk_emit (more
+// than 8 values, SH_BK_EMIT_SPEC=0) or none, -1 the generic one because that compile
+// failed (message in sh_last_error)
+int shx_bucket_emit_status(sh_handle* h) {
+    if (!h) return 0;
+    if (h->bk_emit_last < 0) h->err = h->bk_emit_err;
+    return h->bk_emit_last;
+}
+
 // 1: the last general-engine sh_run_device took the rise-and-fall sequence engine
 int shx_seq3_status(sh_handle* h) { return h ? (h->s3b_last ? 2 : h->seq3_last) : 0; }
 // aggregators of the last sh_run_device: 0 none on a fast engine, 1 the post-pass
@@ -1949,6 +1960,59 @@ int shx_bucket_compile(sh_handle* h, char* buf, int64_t len) {
         buf[k] = 0;
     }
     if (shj_bucket_compile(&P, ms, n_ms, &err)) return fail(h, SH_E_HIP, err);
+    return SH_OK;
+}
+
+static void copy_text(const std::string& t, char* buf, int64_t len) {
+    if (!buf || len <= 0) return;
+    const int64_t k = std::min<int64_t>(len - 1, (int64_t)t.size());
+    memcpy(buf, t.data(), k);
+    buf[k] = 0;
+}
+
+// compile-only check of the specialised emitter (no device needed) of the handle's
+// window-shaped select in one output layout (SHB_OUT_*), as run_bucket would ask for
+// it without carried aggregates; buf takes the generated source
+int shx_emit_compile(sh_handle* h, int layout, char* buf, int64_t len) {
+    if (!h) return SH_E_INVALID_ARG;
+    const shp_program& P = h->prog;
+    if (!P.window_ok || !P.out_fast) return fail(h, SH_E_UNSUPPORTED, "not a window-shaped projection");
+    if (layout < SHB_OUT_RAW || layout > SHB_OUT_PACKED) return fail(h, SH_E_INVALID_ARG, "layout");
+    const void* cols[32] = {};  // (shp_program.attr_type: 32 attributes per stream)
+    shb_out O;
+    shb_select S;
+    if (shb_plan_select(P, h->part_attr0, cols, &O, &S)) return fail(h, SH_E_UNSUPPORTED, "too many match-stream columns");
+    shb_cols OC{};
+    OC.use = layout;
+    int32_t w[SHB_MAX_OUT], woff[SHB_MAX_OUT], rw = 0;
+    for (int o = 0; o < O.n_out; o++) w[o] = type_width(O.type[o]);
+    packed_layout(w, O.n_out, woff, &rw);
+    for (int o = 0; o < O.n_out; o++) {
+        OC.colw[o] = layout == SHB_OUT_RAW ? 0 : w[o];
+        OC.woff[o] = layout == SHB_OUT_PACKED ? woff[o] : 0;
+    }
+    OC.rw = layout == SHB_OUT_PACKED ? rw : 0;
+    shj_emit_key K;
+    if (shj_emit_key_of(&O, &OC, &K)) return fail(h, SH_E_UNSUPPORTED, "no specialised emitter for this select list");
+    std::string src, name, err;
+    shj_emit_source(&K, &src, &name);
+    copy_text(src, buf, len);
+    if (shj_emit_compile(&K, &err)) return fail(h, SH_E_HIP, err);
+    return SH_OK;
+}
+
+// the same from the key's own words (shj_emit_key: mode, values, row words, then kind,
+// type, word offset and width of 8 values each); err takes the compiler's message
+int shx_emit_compile_key(const int32_t* key, char* buf, int64_t len, char* err, int64_t err_len) {
+    shj_emit_key K;
+    memcpy(&K, key, sizeof(K));
+    std::string src, name, e;
+    if (shj_emit_source(&K, &src, &name)) return SH_E_UNSUPPORTED;
+    copy_text(src, buf, len);
+    if (shj_emit_compile(&K, &e)) {
+        copy_text(e, err, err_len);
+        return SH_E_HIP;
+    }
     return SH_OK;
 }
 

@@ -1147,6 +1147,35 @@ static int bk_close(sh_handle* h, sh_device_run* run, int32_t flag, int64_t tota
     return hipStreamSynchronize(st) == hipSuccess ? SH_OK : fail(h, SH_E_HIP, what);
 }
 
+// The emitter of a run's select list and layout: the kernel hipRTC compiles for them
+// (sh_jit.cpp gen_emit; compiled at the first run of a layout, kept on the handle), or
+// nullptr for the generic k_bk_emit: lists of more than 8 values, a failed compile, and
+// SH_BK_EMIT_SPEC=0 (read per call). Sets bk_emit_last
+static void* bk_emit_fn(sh_handle* h, const shb_out& O, const shb_cols& OC) {
+    h->bk_emit_last = 0;
+    if (const char* e = getenv("SH_BK_EMIT_SPEC"))
+        if (atoi(e) == 0) return nullptr;
+    shj_emit_key K;
+    if (shj_emit_key_of(&O, &OC, &K)) return nullptr;
+    const sh_handle::BkEmit* hit = nullptr;
+    for (const auto& c : h->bk_emit)
+        if (!memcmp(&c.key, &K, sizeof(K))) hit = &c;
+    if (!hit) {
+        void* fn = nullptr;
+        if (shj_emit_load(&K, &fn, &h->bk_emit_err)) fn = nullptr;
+        h->bk_emit.push_back({K, fn});
+        hit = &h->bk_emit.back();
+    }
+    h->bk_emit_last = hit->fn ? 1 : -1;
+    return hit->fn;
+}
+
+static int bk_emit(void* fn, const shb_plan& B, const shb_out& O, const shb_cols& OC, sh_device_run* run,
+                   hipStream_t stream) {
+    return fn ? shb_emit_spec(fn, &B, &O, &OC, 0, run->d_out_seq, run->d_out_values, run->out_capacity, stream)
+              : shb_emit(&B, &O, &OC, 0, run->d_out_seq, run->d_out_values, run->out_capacity, stream);
+}
+
 // chunks per time segment of run_bucket's matcher / emitter pipeline (C2: 8 chunks 3.90 ms
 // per step, 16 3.70, 32 3.66-3.68 against the single launch's 3.70-3.74,
 // profiles/c2_pipeline_ab.txt)
@@ -1159,6 +1188,7 @@ static int bucket_launch(sh_handle* h, sh_device_run* run, shb_plan& B, const sh
                          const shb_aggc* AG) {
     hipStream_t st = h->stream;
     void* args[] = {&B};
+    void* const efn = bk_emit_fn(h, O, OC);
     // The matcher (VALU and LDS bound) and the emitter (parked on memory) overlap over
     // time segments of whole chunks: the matchers of segment 0, 1, ... on the caller's
     // stream, an event after each; behind that event, on the handle's side stream, the
@@ -1205,7 +1235,7 @@ static int bucket_launch(sh_handle* h, sh_device_run* run, shb_plan& B, const sh
             if (hipEventRecord(h->bk_ev[k], st) != hipSuccess || hipStreamWaitEvent(sd, h->bk_ev[k], 0) != hipSuccess)
                 return quit("bucket segment event");
             if (shb_finish_seg(&B, B.et0, B.et1, B.ms_ctr + 2, k == n_seg - 1, sd)) return quit("bucket scan launch failed");
-            if (shb_emit(&B, &O, &OC, 0, run->d_out_seq, run->d_out_values, run->out_capacity, sd))
+            if (bk_emit(efn, B, O, OC, run, sd))
                 return quit("bucket emit launch failed");
         }
         // advance_ms: the matchers (and what of the emitters ran beside them); emit_ms:
@@ -1221,8 +1251,7 @@ static int bucket_launch(sh_handle* h, sh_device_run* run, shb_plan& B, const sh
         if (AG && shb_agg_carry(&B, AG, st)) return fail(h, SH_E_HIP, "aggregate carry launch failed");
         if (shb_finish(&B, h->w_scan.as<uint32_t>(), st)) return fail(h, SH_E_HIP, "bucket scan launch failed");
         hipEventRecord(h->ev[2], st);
-        if (shb_emit(&B, &O, &OC, 0, run->d_out_seq, run->d_out_values, run->out_capacity, st))
-            return fail(h, SH_E_HIP, "bucket emit launch failed");
+        if (bk_emit(efn, B, O, OC, run, st)) return fail(h, SH_E_HIP, "bucket emit launch failed");
     }
     return SH_OK;
 }
@@ -1238,6 +1267,7 @@ static int bucket_launch(sh_handle* h, sh_device_run* run, shb_plan& B, const sh
 int run_bucket(sh_handle* h, sh_device_run* run, int32_t nkeys, BkAgg mode, BkRun* res) {
     static const bool off = getenv("SH_DISABLE_BUCKET") != nullptr;
     h->bk_last = 0;
+    h->bk_emit_last = 0;
     *res = BkRun{};
     const shp_program& P = h->prog;
     const int64_t n = run->n;
@@ -1371,6 +1401,7 @@ int run_bucket(sh_handle* h, sh_device_run* run, int32_t nkeys, BkAgg mode, BkRu
 int run_s3b(sh_handle* h, sh_device_run* run, int32_t nkeys) {
     const bool off = getenv("SH_DISABLE_S3B") != nullptr || getenv("SH_NO_SEQ3") != nullptr;  // (per call: tests A/B it)
     h->s3b_last = 0;
+    h->bk_emit_last = 0;
     if (off || !h->partitioned || h->T->n_queries != 1 || !h->T->q[0].s3 || nkeys < 1024 || run->n < SHB_TILE)
         return 1;
     const nf_query& Q = h->T->q[0];
@@ -1434,8 +1465,7 @@ int run_s3b(sh_handle* h, sh_device_run* run, int32_t nkeys) {
     if (shb_s3_carry(&B, &S, st)) return fail(h, SH_E_HIP, "sequence carry launch failed");
     if (shb_finish(&B, h->w_scan.as<uint32_t>(), st)) return fail(h, SH_E_HIP, "sequence scan failed");
     hipEventRecord(h->ev[2], st);
-    if (shb_emit(&B, &O, &OC, 0, run->d_out_seq, run->d_out_values, run->out_capacity, st))
-        return fail(h, SH_E_HIP, "sequence emit failed");
+    if (bk_emit(bk_emit_fn(h, O, OC), B, O, OC, run, st)) return fail(h, SH_E_HIP, "sequence emit failed");
     int32_t flag = 0;
     int64_t total = 0;
     if (const int erc = bk_end(h, &B, "device error in the sequence engine", &flag, &total)) return erc;

@@ -406,6 +406,15 @@ struct sh_handle {
     static constexpr int SH_BK_SEGS = 64;
     hipStream_t bk_side = nullptr;
     hipEvent_t bk_ev[SH_BK_SEGS + 1] = {};
+    // the emitter compiled for a (select list, layout) at its first run (shj_emit_load);
+    // fn NULL: that compile failed (bk_emit_err) and the generic k_bk_emit runs
+    struct BkEmit {
+        shj_emit_key key;
+        void* fn;
+    };
+    std::vector<BkEmit> bk_emit;
+    std::string bk_emit_err;
+    int bk_emit_last = 0;     // the last run_bucket / run_s3b emitter: 1 specialised, 0 generic, -1 generic after a failed compile
     bool aggp_refused = false;  // run_bucket: k_bk_aggp refused a value once: the post-pass from then on
     // typed output columns (sh_device_run.d_out_cols) for engines that write rows
     DevBuf w_colrows;
@@ -595,5 +604,8 @@ int64_t shx_rules_agg_capacity(sh_handle* h);
 int shx_host_profile(sh_handle* h, double* ms, int64_t* n, int cap);
 int shx_seq3_shape(sh_handle* h);
 int shx_bucket_compile(sh_handle* h, char* buf, int64_t len);
+int shx_bucket_emit_status(sh_handle* h);
+int shx_emit_compile(sh_handle* h, int layout, char* buf, int64_t len);
+int shx_emit_compile_key(const int32_t* key, char* buf, int64_t len, char* err, int64_t err_len);
 int64_t shx_jit_source(sh_handle* h, char* buf, int64_t len);
 }

@@ -1385,6 +1385,51 @@ uint32_t k = 0;
     return true;
 }
 
+// ---- the bucketed emitter per (select list, output layout): sh_bk_emit.h behind the
+// list's descriptor tables, and one extern "C" kernel whose arguments are the plan and
+// the pointers alone
+
+// 4-byte words a row's values hold in registers at their natural width
+int emit_words(const shj_emit_key& K) {
+    int wds = 0;
+    for (int o = 0; o < K.no; o++) wds += type_width(K.type[o]) == 8 ? 2 : 1;
+    return wds;
+}
+
+bool gen_emit(const shj_emit_key& K, std::string& src, std::string& name) {
+    if (K.no < 1 || K.no > SHJ_EMIT_MAX || K.mode < SHB_OUT_RAW || K.mode > SHB_OUT_PACKED) return false;
+    // (keys also arrive from tools, shx_emit_compile_key: nothing a kernel would index with is taken unchecked)
+    if (K.mode == SHB_OUT_PACKED ? (K.rw < 4 || K.rw % 4 || K.rw > 2 + 2 * K.no + 2) : K.rw != 0) return false;
+    for (int o = 0; o < K.no; o++) {
+        const int cw = K.colw[o];
+        if (K.type[o] < SH_T_STRING || K.type[o] > SH_T_BOOL || (K.kind[o] != 0 && K.kind[o] != 1)) return false;
+        if (K.mode == SHB_OUT_RAW ? cw != 0 : (cw != 1 && cw != 4 && cw != 8)) return false;
+        if (K.mode == SHB_OUT_PACKED ? (K.woff[o] < 2 || K.woff[o] + (cw == 8 ? 2 : 1) > K.rw) : K.woff[o] != 0)
+            return false;
+    }
+    int occ = 0, ru = 0;
+    shj_emit_form(&K, &occ, &ru);
+    auto table = [&](const char* nm, const int32_t* v) {
+        std::string t = std::string("static __device__ constexpr int32_t ") + nm + "[BKS_NO] = {";
+        for (int o = 0; o < K.no; o++) t += (o ? ", " : "") + std::to_string(v[o]);
+        return t + "};\n";
+    };
+    name = "k_bk_emit_" + std::to_string(K.mode) + "_" + std::to_string(K.no) + "_" + std::to_string(ru) + "_" +
+           std::to_string(occ);
+    std::string g = SHJ_HEADERS;
+    g += "\n// ---- the select list's descriptors (sh_rows.h reads them through BK_KIND .. BK_RW)\n";
+    g += "#define BKS_NO " + std::to_string(K.no) + "\n";
+    g += "#define BKS_MODE " + std::to_string(K.mode) + "\n";
+    g += "#define BKS_RW " + std::to_string(K.rw) + "\n";
+    g += "#define BKS_RU " + std::to_string(ru) + "\n";
+    g += "#define BKS_OCC " + std::to_string(occ) + "\n";
+    g += "#define BKS_NAME " + name + "\n";
+    g += table("BKS_KIND", K.kind) + table("BKS_TYPE", K.type) + table("BKS_WOFF", K.woff) + table("BKS_COLW", K.colw);
+    g += SHJ_EMIT_SRC;
+    src.swap(g);
+    return true;
+}
+
 struct Entry {
     int status = 0;           // 0 ok, <0 failed (message in err)
     std::string err;
@@ -1533,6 +1578,86 @@ int shj_bucket_compile(const shp_program* hp, const int* ms_attrs, int n_ms, std
     Entry* e = compile(src);
     if (e->status && err) *err = e->err;
     return e->status;
+}
+
+int shj_emit_key_of(const shb_out* O, const shb_cols* OC, shj_emit_key* K) {
+    memset(K, 0, sizeof(*K));
+    const int use = OC ? OC->use : SHB_OUT_RAW;
+    if (O->n_out < 1 || O->n_out > SHJ_EMIT_MAX) return -1;
+    if (use == SHB_OUT_PACKED && (OC->rw % 4 || OC->rw < 4 || OC->rw > 2 + 2 * O->n_out + 2)) return -1;
+    K->mode = use;
+    K->no = O->n_out;
+    K->rw = use == SHB_OUT_PACKED ? OC->rw : 0;
+    for (int o = 0; o < O->n_out; o++) {
+        K->kind[o] = O->kind[o] == 1 ? 1 : 0;
+        K->type[o] = O->type[o];
+        K->woff[o] = use == SHB_OUT_PACKED ? OC->woff[o] : 0;
+        K->colw[o] = use == SHB_OUT_RAW ? 0 : OC->colw[o];
+    }
+    return 0;
+}
+
+// The occupancy form is bk_emit_launch's (sh_bucket.hip): 6 waves per SIMD (80 VGPRs)
+// for raw / packed rows of at most 5 values and typed columns of at most 2, else 4
+// waves (128). Rows per lane and round: the generic kernel's count where the
+// specialised one compiles for gfx950 without VGPR spills or scratch inside that
+// budget, fewer where it does not (scripts/emit_spec_resources.py compiles every form
+// of tests/emit_cases.py, all-4-byte and all-8-byte lists of each width and the
+// benchmark's forms; the table is in profiles/c2_emit_spec_ab.txt). C2 (packed, 4
+// values) fits 4 rows where the generic kernel fits 3; measured, 4 ties with 3
+// (3.372 against 3.363 ms per step), so it stays at 3
+void shj_emit_form(const shj_emit_key* K, int* occ, int* ru) {
+    const int no = K->no, mode = K->mode;
+    const bool wide3 = no == 3 && emit_words(*K) > 4;  // three values, 8-byte ones among them
+    const bool six = mode == SHB_OUT_COLS ? no <= 2 : no <= 5;
+    *occ = six ? 6 : 4;
+    if (mode == SHB_OUT_COLS)
+        *ru = no == 3 ? 6 : (no <= 4 ? 4 : (no == 5 ? 2 : 1));
+    else if (mode == SHB_OUT_PACKED)
+        *ru = no <= 3 ? (wide3 ? 2 : 4) : (no == 5 || no == 7 ? 2 : (no == 8 ? 1 : 3));  // (6 values: the generic 4 spills)
+    else
+        *ru = no <= 3 ? (wide3 ? 2 : 4) : (no == 4 ? 2 : (no == 5 ? 1 : (no == 6 ? 3 : (no == 7 ? 2 : 1))));
+}
+
+int shj_emit_source(const shj_emit_key* K, std::string* src, std::string* name) {
+    return gen_emit(*K, *src, *name) ? 0 : -1;
+}
+
+int shj_emit_compile(const shj_emit_key* K, std::string* err) {
+    std::string src, name;
+    if (!gen_emit(*K, src, name)) {
+        if (err) *err = "no specialised emitter for this select list";
+        return -1;
+    }
+    Entry* e = compile(src);
+    if (e->status && err) *err = e->err;
+    return e->status;
+}
+
+int shj_emit_load(const shj_emit_key* K, void** fn, std::string* err) {
+    *fn = nullptr;
+    std::string src, name;
+    if (!gen_emit(*K, src, name)) {
+        if (err) *err = "no specialised emitter for this select list";
+        return -1;
+    }
+    Entry* e = compile(src);
+    if (e->status) {
+        if (err) *err = e->err;
+        return e->status;
+    }
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (!e->mod) {
+        if (hipModuleLoadData(&e->mod, e->code.data()) != hipSuccess ||
+            hipModuleGetFunction(&e->emit, e->mod, name.c_str()) != hipSuccess) {
+            if (err) *err = "hipModuleLoadData/GetFunction (" + name + ") failed";
+            e->mod = nullptr;
+            (void)hipGetLastError();
+            return -3;
+        }
+    }
+    *fn = e->emit;
+    return 0;
 }
 
 unsigned shj_tiles(int64_t n, uint32_t* tiles_per_xcd, uint32_t* ntiles) {

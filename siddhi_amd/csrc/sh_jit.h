@@ -5,6 +5,7 @@
 
 #include <string>
 
+#include "sh_device.h"
 #include "sh_program.h"
 
 struct shj_window {
@@ -41,3 +42,27 @@ struct shj_bucket {
 int shj_bucket_load(const shp_program* hp, const int* ms_attrs, int n_ms, shj_bucket* out, std::string* err);
 int shj_bucket_source(const shp_program* hp, const int* ms_attrs, int n_ms, std::string* src);
 int shj_bucket_compile(const shp_program* hp, const int* ms_attrs, int n_ms, std::string* err);
+
+// bucketed emitter (sh_bk_emit.h) compiled for one select list and output layout: the
+// descriptors k_bk_emit reads from its arguments become constants of the kernel.
+// Lists of 1 .. SHJ_EMIT_MAX values; longer ones keep the generic kernel
+#define SHJ_EMIT_MAX 8
+struct shj_emit_key {
+    int32_t mode;                  // SHB_OUT_*
+    int32_t no;                    // select values
+    int32_t rw;                    // packed: words per row
+    int32_t kind[SHJ_EMIT_MAX];    // shb_out.kind
+    int32_t type[SHJ_EMIT_MAX];    // shb_out.type
+    int32_t woff[SHJ_EMIT_MAX];    // packed: shb_cols.woff
+    int32_t colw[SHJ_EMIT_MAX];    // packed / typed columns: shb_cols.colw
+};
+// the key of a launch's descriptors (unused fields zero, so keys compare by memcmp);
+// -1: no specialised form (the value count, or a packed row the emitter does not take)
+int shj_emit_key_of(const shb_out* O, const shb_cols* OC, shj_emit_key* K);
+// occupancy form (waves per SIMD: 6 or 4, as bk_emit_launch chooses it) and rows per lane and round
+void shj_emit_form(const shj_emit_key* K, int* occ, int* ru);
+// generated source and the kernel's name (no device needed)
+int shj_emit_source(const shj_emit_key* K, std::string* src, std::string* name);
+int shj_emit_compile(const shj_emit_key* K, std::string* err);
+// compile + load on the current device; *fn: hipFunction_t for shb_emit_spec
+int shj_emit_load(const shj_emit_key* K, void** fn, std::string* err);

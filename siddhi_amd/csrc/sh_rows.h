@@ -8,6 +8,35 @@
 #include "../../include/sh_query.h"
 #include "sh_device.h"
 
+// The select's descriptors as the row code reads them. The generic build reads the
+// kernel arguments (O: shb_out, OC: shb_cols, both in scope at every use). A
+// specialised build (sh_jit.cpp, one kernel per select list and layout) defines
+// BKS_NO (the value count) before this text, with the constexpr tables BKS_KIND,
+// BKS_TYPE, BKS_WOFF, BKS_COLW and the constants BKS_RW and BKS_MODE: every read
+// below is then a compile-time constant, and O and OC are one block of pointers.
+#ifdef BKS_NO
+#define BK_KIND(o) BKS_KIND[o]
+#define BK_TYPE(o) BKS_TYPE[o]
+#define BK_WOFF(o) BKS_WOFF[o]
+#define BK_COLW(o) BKS_COLW[o]
+#define BK_RW BKS_RW
+struct bks_ptrs {
+    const void* src[BKS_NO];  // shb_out.src
+    void* cols[BKS_NO];       // shb_cols.cols (typed columns)
+    void* rows;               // shb_cols.rows (packed rows)
+};
+typedef bks_ptrs bk_out_t;
+typedef bks_ptrs bk_cols_t;
+#else
+#define BK_KIND(o) O.kind[o]
+#define BK_TYPE(o) O.type[o]
+#define BK_WOFF(o) OC.woff[o]
+#define BK_COLW(o) OC.colw[o]
+#define BK_RW OC.rw
+typedef shb_out bk_out_t;
+typedef shb_cols bk_cols_t;
+#endif
+
 // raw 8-byte value of a column element (the VmVal bits sh_vm.h load_attr forms)
 __device__ __forceinline__ int64_t bk_raw(const void* p, int64_t i, int type) {
     switch (type) {
@@ -35,16 +64,16 @@ __device__ __forceinline__ void bk_put(void* col, int w, int64_t row, int64_t v)
 // each select value at its natural width in OC.woff[o] (8-byte values at even
 // words), OC.rw words per row (a multiple of 4: whole 16-byte stores). Value o
 // sits in words [2 + o, 2 + 2o] (every earlier value one word .. two), so only
-// those candidates are tested: the offsets are kernel arguments (scalar), the
-// row stays in registers.
+// those candidates are tested: the offsets are kernel arguments (scalar) or, in a
+// specialised build, constants; the row stays in registers.
 template <int NO>
-__device__ __forceinline__ void bk_pack(const shb_cols& OC, int64_t row, const int64_t* v, uint64_t seq) {
+__device__ __forceinline__ void bk_pack(const bk_cols_t& OC, int64_t row, const int64_t* v, uint64_t seq) {
     constexpr int RW = ((2 + 2 * NO) + 3) & ~3;
-    uint4* dst = (uint4*)((uint32_t*)OC.rows + row * OC.rw);
+    uint4* dst = (uint4*)((uint32_t*)OC.rows + row * BK_RW);
     // one 16-byte store at a time: only its four words live (registers for more rows in flight)
 #pragma unroll
     for (int q = 0; q < RW / 4; q++) {
-        if (4 * q >= OC.rw) break;
+        if (4 * q >= BK_RW) break;
         uint32_t wv[4] = {0u, 0u, 0u, 0u};
         if (q == 0) {
             wv[0] = (uint32_t)seq;
@@ -52,9 +81,9 @@ __device__ __forceinline__ void bk_pack(const shb_cols& OC, int64_t row, const i
         }
 #pragma unroll
         for (int o = 0; o < NO; o++) {
-            const int wo = OC.woff[o];
-            const bool wide = OC.colw[o] == 8;
-            const uint32_t lo = OC.colw[o] == 1 ? (uint32_t)(uint8_t)v[o] : (uint32_t)v[o];
+            const int wo = BK_WOFF(o);
+            const bool wide = BK_COLW(o) == 8;
+            const uint32_t lo = BK_COLW(o) == 1 ? (uint32_t)(uint8_t)v[o] : (uint32_t)v[o];
             const uint32_t hi = (uint32_t)((uint64_t)v[o] >> 32);
 #pragma unroll
             for (int k = 2 + o; k <= 2 + 2 * o && k < RW; k++)
@@ -70,7 +99,7 @@ __device__ __forceinline__ void bk_pack(const shb_cols& OC, int64_t row, const i
 // one row in the caller's layout (MODE: SHB_OUT_RAW 8-byte words + out_seq,
 // SHB_OUT_COLS natural-width columns + out_seq, SHB_OUT_PACKED rows)
 template <int MODE, int NO>
-__device__ __forceinline__ void bk_store(const shb_cols& OC, int64_t row, const int64_t* v, uint64_t seq,
+__device__ __forceinline__ void bk_store(const bk_cols_t& OC, int64_t row, const int64_t* v, uint64_t seq,
                                          uint64_t* __restrict__ out_seq, int64_t* __restrict__ out_vals) {
     if (MODE == SHB_OUT_PACKED) {
         bk_pack<NO>(OC, row, v, seq);
@@ -79,7 +108,7 @@ __device__ __forceinline__ void bk_store(const shb_cols& OC, int64_t row, const 
     if (out_seq) out_seq[row] = seq;
     if (MODE == SHB_OUT_COLS) {
 #pragma unroll
-        for (int o = 0; o < NO; o++) bk_put(OC.cols[o], OC.colw[o], row, v[o]);
+        for (int o = 0; o < NO; o++) bk_put(OC.cols[o], BK_COLW(o), row, v[o]);
     } else if (out_vals) {
         if (NO % 2 == 0) {
             // a row of NO words as 16-byte stores: consecutive lanes fill whole lines

@@ -174,6 +174,13 @@ class DeviceRunner:
         shb_match), 0: another engine."""
         return lib().shx_bucket_status(self.handle.h)
 
+    def bucket_emit_status(self):
+        """the emitter launched by the last run that reached the bucketed or the sequence
+        bucket-carry engine: 1 the kernel compiled for its select list and layout, 0 the
+        generic k_bk_emit (or none), -1 the generic one because that compile failed
+        (last_error())."""
+        return lib().shx_bucket_emit_status(self.handle.h)
+
     def seq3_status(self):
         """1: the last run took the rise-and-fall sequence engine (k_seq3)."""
         return lib().shx_seq3_status(self.handle.h)
