@@ -390,13 +390,14 @@ static int lower_chain(sh_handle* h, const sh_app_desc* app, int qi, shp_program
 }
 
 // order by / limit / offset / group by, List outputs, a `having` that reads a
-// state-event attribute and the limiters `output all every N events` / `output first
-// every T` need the selector pass of the general engine (SHX_GENERAL). A `having` over
-// output attributes and constants alone is a predicate of the finished row
-// (sh_having.h), and `output first|last every N events` a function of the row's ordinal
-// in its (query, key) (sh_rate.h): the fast engines take the app, with the device row
-// filter (SHX_HAVING: its programs in *progs, one per query) and the limiter pass
-// (SHX_RATE: its rules in *rules, one per query) behind them. 0: none of these
+// state-event attribute and the time limiter `output first every T` need the selector
+// pass of the general engine (SHX_GENERAL). A `having` over output attributes and
+// constants alone is a predicate of the finished row (sh_having.h), and `output
+// first|last|all every N events` a function of the row's ordinal in its (query, key)
+// (sh_rate.h; `all` moves rows to their chunk's N-th instead of dropping them): the
+// fast engines take the app, with the device row filter (SHX_HAVING: its programs in
+// *progs, one per query) and the limiter pass (SHX_RATE: its rules in *rules, one per
+// query) behind them. 0: none of these
 enum { SHX_HAVING = 1, SHX_RATE = 2, SHX_GENERAL = 4 };
 static int selector_extras(const sh_app_desc* app, std::vector<shv_prog>* progs, std::vector<shl_rule>* rules) {
     int extras = 0;
@@ -410,10 +411,10 @@ static int selector_extras(const sh_app_desc* app, std::vector<shv_prog>* progs,
             if (d.outputs[o].expr >= 0 && d.outputs[o].expr < d.n_exprs && d.exprs[d.outputs[o].expr].op == SH_OP_MULTI_VAR)
                 return SHX_GENERAL;
         if (d.rate_kind != SH_RATE_NONE) {
-            // (`all every N` reorders: held rows leave with the N-th; `first every T`
-            // reads the playback clock per call)
-            if ((d.rate_kind != SH_RATE_FIRST_EVENTS && d.rate_kind != SH_RATE_LAST_EVENTS) || d.rate_value < 1 ||
-                getenv("SH_NO_RATE_FILTER"))
+            // (`first every T` reads the playback clock per call)
+            if ((d.rate_kind != SH_RATE_FIRST_EVENTS && d.rate_kind != SH_RATE_LAST_EVENTS &&
+                 d.rate_kind != SH_RATE_ALL_EVENTS) ||
+                d.rate_value < 1 || getenv("SH_NO_RATE_FILTER"))
                 return SHX_GENERAL;
             if (rules) (*rules)[q] = shl_rule{d.rate_kind, d.rate_value};
             extras |= SHX_RATE;
@@ -435,7 +436,7 @@ static int compile_chain(sh_handle* h, const sh_app_desc* app) {
     const int extras = selector_extras(app, &hv, &rl);
     if (extras & SHX_GENERAL)
         return fail(h, SH_E_UNSUPPORTED, "chain engine: order by / limit / a having over state-event attributes / "
-                                         "time and all-events limiters run on the general engine");
+                                         "time limiters run on the general engine");
     shp_program P;
     int rc = lower_chain(h, app, 0, P);
     if (rc) return rc;
@@ -491,7 +492,14 @@ static int compile_rules(sh_handle* h, const sh_app_desc* app) {
     const int extras = selector_extras(app, &hv, &rl);
     if (extras & SHX_GENERAL)
         return fail(h, SH_E_UNSUPPORTED, "rule engine: order by / limit / a having over state-event attributes / time "
-                                         "and all-events limiters run on the general engine");
+                                         "limiters run on the general engine");
+    // `all every N` holds rows back: a set that only this engine can stream (beyond the
+    // general engine's query table) would have to carry them between steps and in snapshots
+    if (app->n_queries > NF_MAX_QUERIES)
+        for (const shl_rule& R : rl)
+            if (shl_holds(R))
+                return fail(h, SH_E_UNSUPPORTED, "rule engine: `output all every N events` on more than 16 queries "
+                                                 "(held rows are not carried between steps)");
     const int part = app->queries[0].partition;
     std::vector<shr_rule> rules(app->n_queries);
     std::unique_ptr<sh_handle> tmp(new sh_handle());

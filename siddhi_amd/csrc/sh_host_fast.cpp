@@ -675,8 +675,9 @@ int rate_limit(sh_handle* h, int64_t m, int n_out, const shw_rows& src, const in
     for (auto& e : S.ev)
         if (!e) hipEventCreate(&e);
     hipEventRecord(S.ev[0], h->stream);
-    if (shl_limit(h->rl_d_rules.as<shl_rule>(), (int32_t)h->rl_rules.size(), m, n_out, &src, keys, n_keys, 0, T, &dst,
-                  S.ws.as<uint32_t>(), S.kept.as<unsigned long long>(), h->stream, put_keys, put_state))
+    if (shl_limit_rules(h->rl_rules.data(), h->rl_d_rules.as<shl_rule>(), (int32_t)h->rl_rules.size(), m, n_out, &src,
+                        keys, n_keys, 0, T, &dst, S.ws.as<uint32_t>(), S.kept.as<unsigned long long>(), h->stream,
+                        put_keys, put_state))
         return fail(h, SH_E_HIP, "event limiter launch failed");
     hipEventRecord(S.ev[1], h->stream);
     return SH_OK;

@@ -1,5 +1,5 @@
-// sh_rate.hip — `output first|last every N events` behind the fast engines: the keep
-// rule of sh_rate.h applied to the ordered raw rows an engine produced (after
+// sh_rate.hip — `output first|last|all every N events` behind the fast engines: the
+// rules of sh_rate.h applied to the ordered raw rows an engine produced (after
 // `having`), as a segmented rank followed by a stable compaction.
 //
 //   k_shl_prep    one lane per row: the row's index and its sort key, query << kbits |
@@ -23,10 +23,27 @@
 //   k_shl_mark    64-bit ballots of the keep bytes and one kept count per tile of
 //                 SHV_TILE rows, then shv_move_marked (sh_having.hip): scan and move
 //
+// A set with an `output all every N events` rule (shl_holds) places rows instead
+// (shl_place, sh_rate.h): the same prep, sort, tile and carry, then
+//   k_shl_rel     in place of k_shl_out: per row, in row order, its release row (the
+//                 row index `ahead` places on in its run, SHL_NO_ROW when it stays
+//                 held or is dropped), its offset among the rows released there, and
+//                 its own weight, the number of rows it releases
+//   (scan)        shd_exclusive_scan of the weights in row order: where every row's
+//                 released rows start in the output
+//   k_shl_src     one lane per row: src_of[start of its release row + offset] = row (the
+//                 only scattered store), and the last row's start + weight to *d_kept
+//   k_shl_move    one workgroup per tile of SHV_TILE output rows, as k_shv_move with
+//                 the tile's sources read from src_of: a lane per row for the 4- and
+//                 8-byte columns, lanes across the rows' words for values and null
+//                 flags, so every store is coalesced and the gathers read whole rows
+//
 // The pair of a head at position 0 with counter 0 is the scan's identity, which is
 // what a row before any head of its tile has until the carry reaches it.
 #include <hip/hip_runtime.h>
 #include <string.h>
+
+#include <vector>
 
 #include "sh_agg_seq.h"
 #include "sh_device.h"
@@ -207,6 +224,90 @@ __global__ void __launch_bounds__(SHL_TPB) k_shl_out(const uint32_t* __restrict_
     }
 }
 
+#define SHL_NO_ROW 0xFFFFFFFFu
+
+// rel[r] / choff[r] / wgt[r] of row r = idx[p]: shl_place on its ordinal (every run
+// starts from zero); a row `ahead` of its release row leaves only if that position is
+// still in its run
+__global__ void __launch_bounds__(SHL_TPB) k_shl_rel(const uint32_t* __restrict__ s32,
+                                                     const uint64_t* __restrict__ s64, int kbits,
+                                                     const uint32_t* __restrict__ idx, int64_t m,
+                                                     const shl_rule* __restrict__ rules, int32_t n_rules,
+                                                     const uint64_t* __restrict__ loc,
+                                                     const uint64_t* __restrict__ tiles, uint32_t* __restrict__ rel,
+                                                     uint32_t* __restrict__ choff, uint32_t* __restrict__ wgt) {
+    const int64_t p = (int64_t)blockIdx.x * SHL_TPB + threadIdx.x;
+    if (p >= m) return;
+    const uint64_t sg = shl_run_key(s32, s64, kbits, p);
+    const uint64_t v = shl_max(loc[p], tiles[p / SHL_TILE]);
+    const uint64_t j = (uint64_t)(p - (int64_t)(v >> 32)) + 1ull;
+    const int32_t q = (int32_t)(sg >> 32);
+    shl_rule R;
+    R.kind = SH_RATE_NONE;
+    R.n = 0;
+    if (q >= 0 && q < n_rules) R = rules[q];
+    const shl_spot S = shl_place(R, j);
+    const int64_t pr = p + (int64_t)S.ahead;
+    const bool leaves = S.leaves && pr < m && (S.ahead == 0 || shl_run_key(s32, s64, kbits, pr) == sg);
+    const uint32_t r = idx[p];
+    rel[r] = leaves ? idx[pr] : SHL_NO_ROW;
+    choff[r] = S.offset;
+    wgt[r] = S.weight;
+}
+
+// woff: the exclusive scan of wgt. The places are distinct and below the total, which
+// is at most m: the N rows of a chunk share a release row of weight N and differ in
+// their offsets (the bound checks only keep a fault in that reasoning inside the arrays)
+__global__ void __launch_bounds__(SHL_TPB) k_shl_src(const uint32_t* __restrict__ rel,
+                                                     const uint32_t* __restrict__ choff,
+                                                     const uint32_t* __restrict__ wgt,
+                                                     const uint32_t* __restrict__ woff, int64_t m,
+                                                     uint32_t* __restrict__ src_of,
+                                                     unsigned long long* __restrict__ d_kept) {
+    const int64_t r = (int64_t)blockIdx.x * SHL_TPB + threadIdx.x;
+    if (r >= m) return;
+    if (r == m - 1) {
+        const uint64_t total = (uint64_t)woff[r] + wgt[r];
+        *d_kept = total <= (uint64_t)m ? total : 0ull;
+    }
+    const uint32_t to = rel[r];
+    if (to == SHL_NO_ROW || (int64_t)to >= m) return;
+    const uint64_t d = (uint64_t)woff[to] + choff[r];
+    if (d < (uint64_t)m) src_of[d] = (uint32_t)r;
+}
+
+// output rows [tile * SHV_TILE, ...) from their sources src_of[d] (the two row sets never
+// overlap)
+__global__ void __launch_bounds__(SHV_TILE) k_shl_move(int32_t n_out, int64_t m, shw_rows in, shw_rows_out out,
+                                                       const uint32_t* __restrict__ src_of,
+                                                       const unsigned long long* __restrict__ d_kept) {
+    __shared__ uint32_t src[SHV_TILE];
+    const int64_t total = (int64_t)*d_kept;
+    const int64_t base = (int64_t)blockIdx.x * SHV_TILE;
+    if (base >= total) return;
+    const uint32_t rows = (uint32_t)(total - base < SHV_TILE ? total - base : SHV_TILE);
+    {
+        uint32_t s = threadIdx.x < rows ? src_of[base + threadIdx.x] : 0u;
+        if ((int64_t)s >= m) s = 0u;
+        src[threadIdx.x] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < rows) {
+        const int64_t s = src[threadIdx.x], d = base + threadIdx.x;
+        if (out.seq) out.seq[d] = in.seq[s];
+        if (out.query) out.query[d] = in.query[s];
+        if (out.ts) out.ts[d] = in.ts[s];
+        if (out.key) out.key[d] = in.key[s];
+    }
+    const uint32_t words = rows * (uint32_t)n_out;
+    for (uint32_t w = threadIdx.x; w < words; w += SHV_TILE) {
+        const uint32_t j = w / (uint32_t)n_out, c = w - j * (uint32_t)n_out;
+        const int64_t s = (int64_t)src[j] * n_out + c, d = (base + j) * n_out + c;
+        out.vals[d] = in.vals[s];
+        if (out.nulls) out.nulls[d] = in.nulls[s];
+    }
+}
+
 // the keep bytes (row order) as ballot words and kept counts per tile of SHV_TILE rows
 __global__ void __launch_bounds__(SHV_TILE) k_shl_mark(const uint8_t* __restrict__ keepb, int64_t m,
                                                        uint64_t* __restrict__ mask, uint32_t* __restrict__ cnt) {
@@ -230,6 +331,7 @@ __global__ void __launch_bounds__(SHV_TILE) k_shl_mark(const uint8_t* __restrict
 namespace {
 struct shl_ws {
     uint32_t *klo, *khi, *idx, *gk, *kbuf[2], *vbuf[2], *hist, *stmp, *cnt, *off, *tmp;
+    uint32_t *rel, *choff, *wgt, *woff, *src_of, *ptmp;  // the placement: in pk's and fin's room, and its scan's own
     uint64_t *sseg, *loc, *pk, *tiles, *mask;
     int64_t* fin;
     uint8_t* keepb;
@@ -264,6 +366,12 @@ shl_ws shl_layout(int64_t m, uint8_t* base) {
     W.off = (uint32_t*)take(vt * 4);
     W.tmp = (uint32_t*)take((int64_t)shd_scan_tmp_words(vt) * 4);
     W.keepb = (uint8_t*)take(m);
+    W.ptmp = (uint32_t*)take((int64_t)shd_scan_tmp_words(m) * 4);
+    W.rel = (uint32_t*)W.pk;
+    W.choff = W.rel ? W.rel + m : nullptr;
+    W.wgt = (uint32_t*)W.fin;
+    W.woff = W.wgt ? W.wgt + m : nullptr;
+    W.src_of = W.wgt ? W.wgt + 2 * m : nullptr;
     W.bytes = at;
     return W;
 }
@@ -277,9 +385,28 @@ extern "C" int shl_limit(const shl_rule* rules, int32_t n_rules, int64_t m, int3
                          const int32_t* d_keys, int32_t n_keys, uint64_t seq_base, const shq_table* T,
                          const shw_rows_out* dst, uint32_t* ws, unsigned long long* d_kept, void* stream,
                          const uint64_t** put_keys, const int64_t** put_state) {
+    if (put_keys) *put_keys = nullptr;
+    if (put_state) *put_state = nullptr;
+    if (n_rules < 1 || !rules) return -1;
+    std::vector<shl_rule> h_rules((size_t)n_rules);
+    if (hipMemcpy(h_rules.data(), rules, (size_t)n_rules * sizeof(shl_rule), hipMemcpyDeviceToHost) != hipSuccess)
+        return -3;
+    return shl_limit_rules(h_rules.data(), rules, n_rules, m, n_out, src, d_keys, n_keys, seq_base, T, dst, ws, d_kept,
+                           stream, put_keys, put_state);
+}
+
+extern "C" int shl_limit_rules(const shl_rule* h_rules, const shl_rule* rules, int32_t n_rules, int64_t m,
+                               int32_t n_out, const shw_rows* src, const int32_t* d_keys, int32_t n_keys,
+                               uint64_t seq_base, const shq_table* T, const shw_rows_out* dst, uint32_t* ws,
+                               unsigned long long* d_kept, void* stream, const uint64_t** put_keys,
+                               const int64_t** put_state) {
     hipStream_t st = (hipStream_t)stream;
     if (put_keys) *put_keys = nullptr;
     if (put_state) *put_state = nullptr;
+    if (n_rules < 1 || !rules || !h_rules) return -1;
+    bool holds = false;
+    for (int32_t q = 0; q < n_rules; q++) holds = holds || shl_holds(h_rules[q]);
+    if (holds && (put_keys || put_state || (T && T->cap > 0))) return -1;  // held rows are not carried
     if (!d_kept || m < 0 || m >= 0x7FFFFFFFll || n_out < 1 || n_out > SHV_MAX_OUT || n_rules < 1 || !rules) return -1;
     if (T && T->cap > 0 && ((T->cap & (T->cap - 1)) || T->n_cols != 1 || !T->keys || !T->state)) return -1;
     if (m == 0) return hipMemsetAsync(d_kept, 0, 8, st) == hipSuccess ? 0 : -3;
@@ -327,6 +454,16 @@ extern "C" int shl_limit(const shl_rule* rules, int32_t n_rules, int64_t m, int3
     const bool put = put_keys && put_state;
     hipLaunchKernelGGL(k_shl_tile, dim3((unsigned)nt), dim3(SHL_TPB), 0, st, s32, s64, kbits, m, tab, W.loc, W.tiles);
     hipLaunchKernelGGL(k_shl_carry, dim3(1), dim3(SHL_CARRY_TPB), 0, st, W.tiles, nt);
+    if (holds) {
+        hipLaunchKernelGGL(k_shl_rel, dim3(g), dim3(SHL_TPB), 0, st, s32, s64, kbits, sidx, m, rules, n_rules,
+                           (const uint64_t*)W.loc, (const uint64_t*)W.tiles, W.rel, W.choff, W.wgt);
+        if (shl_ok() || shd_exclusive_scan(W.wgt, W.woff, m, W.ptmp, stream)) return -3;
+        hipLaunchKernelGGL(k_shl_src, dim3(g), dim3(SHL_TPB), 0, st, (const uint32_t*)W.rel, (const uint32_t*)W.choff,
+                           (const uint32_t*)W.wgt, (const uint32_t*)W.woff, m, W.src_of, d_kept);
+        hipLaunchKernelGGL(k_shl_move, dim3((unsigned)vt), dim3(SHV_TILE), 0, st, n_out, m, *src, *dst,
+                           (const uint32_t*)W.src_of, (const unsigned long long*)d_kept);
+        return shl_ok() ? -3 : 0;
+    }
     hipLaunchKernelGGL(k_shl_out, dim3(g), dim3(SHL_TPB), 0, st, s32, s64, kbits, sidx, m, rules, n_rules,
                        (const uint64_t*)W.loc, (const uint64_t*)W.tiles, W.keepb, put ? W.pk : (uint64_t*)nullptr,
                        W.fin);
