@@ -26,7 +26,7 @@ int64_t sha_scratch_bytes(int64_t m, int n_cols);
 // d_query the emitting query or NULL): each listed column's argument values
 // become the running aggregate per (query, partition key of the trigger event
 // = d_keys[seq - seq_base], NULL: one key). 0: done; 1: the double additions
-// would round (or NaN / infinite addends; never for a max / min column, whose value
+// would round or leave the double range (or NaN / infinite addends; never for a max / min column, whose value
 // is the winning argument's raw bits): the rows are as they were, run the
 // query sequentially (sh_agg_seq.h shc_running, or a sequential engine); < 0:
 // error. On 0 the last launch (the rows' scatter) is still in flight on `stream`.

@@ -22,7 +22,9 @@
 // set bit over all addends) and every running value the reference would form
 // is then a multiple of 2^q as well. The sums are taken exactly in 128-bit
 // fixed point (any order), and each running value is checked to be exactly
-// representable as a double (at most 53 significant bits); when all are, every
+// representable as a double (at most 53 significant bits, and below 2^1024 in
+// magnitude: the reference's sum that leaves the double range is an infinity and
+// stays one, whatever the exact sum does next); when all are, every
 // one of the reference's additions was exact and its results equal these bit
 // for bit. Otherwise (or with NaN / infinite addends, or a fixed-point range
 // over 96 bits) the pass reports "not exact" and the caller reruns the query on
@@ -407,7 +409,9 @@ __global__ void __launch_bounds__(SHA_TPB) k_sha_out(int64_t* __restrict__ scol,
                 mlo = mhi >> (tz - 64);
                 mhi = 0ull;
             }
-            if (mhi || mlo >= (1ull << 53)) {
+            // ... and below 2^1024: a sum that leaves the double range is an infinity in
+            // the reference, and stays one when the exact sum comes back
+            if (mhi || mlo >= (1ull << 53) || q + tz + 64 - __builtin_clzll(mlo) > 1024) {
                 atomicOr(flag, 1);
                 return;
             }

@@ -5,9 +5,10 @@ sh_window.hip, called through ctypes with torch device pointers and compared wit
 numpy restatements of what siddhi_amd/csrc/sh_device.h promises.
 
 Held fixed here:
-  * the ctypes mirrors of shd_batch / shd_segment_ws / shd_payload, and of the row
-    sets shw_rows / shw_rows_out of sh_having.h (checked against the headers by
-    tests/prims_layout);
+  * the ctypes mirrors of shd_batch / shd_segment_ws / shd_payload, of the row
+    sets shw_rows / shw_rows_out of sh_having.h, and of sha_col / sha_desc /
+    shq_table of the aggregate post-passes (tests/agg_post_cases.py), all checked
+    against the headers by tests/prims_layout;
   * the numpy contracts (*_ref), written from the header comments, not the kernels;
   * the workspace sizes in 4-byte words as the header and the callers state them.
     Every device buffer has exactly that size plus a guard of GUARD words; outputs
@@ -59,8 +60,27 @@ class shw_rows_out(C.Structure):
     _fields_ = list(shw_rows._fields_)
 
 
+SHA_MAX_COLS = 16
+
+
+class sha_col(C.Structure):
+    """one aggregate output column of the raw rows (sh_agg.h)"""
+    _fields_ = [("col", C.c_int32), ("kind", C.c_int32), ("arg_type", C.c_int32), ("pad", C.c_int32)]
+
+
+class sha_desc(C.Structure):
+    _fields_ = [("n_cols", C.c_int32), ("pad", C.c_int32), ("c", sha_col * SHA_MAX_COLS)]
+
+
+class shq_table(C.Structure):
+    """the carried aggregate states (sh_agg_seq.h): open addressing over the segment key"""
+    _fields_ = [("keys", C.c_void_p), ("state", C.c_void_p), ("cap", C.c_int64), ("n_cols", C.c_int32),
+                ("pad", C.c_int32)]
+
+
 MIRRORS = {"shd_batch": shd_batch, "shd_segment_ws": shd_segment_ws, "shd_payload": shd_payload,
-           "shw_rows": shw_rows, "shw_rows_out": shw_rows_out}
+           "shw_rows": shw_rows, "shw_rows_out": shw_rows_out, "sha_col": sha_col, "sha_desc": sha_desc,
+           "shq_table": shq_table}
 
 _lib = None
 
@@ -86,6 +106,18 @@ def lib():
         L.shd_sort_pairs.restype = C.c_int
         L.shd_tile_dir.argtypes = [vp, C.c_int64, C.c_int, C.c_uint32, C.c_uint32, vp, vp, vp]
         L.shd_tile_dir.restype = C.c_int
+        # the aggregate post-passes (sh_agg.h, sh_agg_seq.h)
+        for f in (L.sha_scratch_bytes, L.shc_scratch_bytes):
+            f.argtypes = [C.c_int64, C.c_int]
+            f.restype = C.c_int64
+        L.sha_running.argtypes = [vp, vp, C.c_int32, C.c_int64, vp, C.c_int32, vp, C.c_int32, C.c_uint64,
+                                  C.POINTER(sha_desc), vp, vp]
+        L.sha_running.restype = C.c_int
+        L.shc_running.argtypes = [vp, vp, C.c_int32, C.c_int64, vp, C.c_int32, vp, vp, C.c_int32, C.c_uint64,
+                                  C.POINTER(sha_desc), C.POINTER(shq_table), vp, vp, pvp, pvp]
+        L.shc_running.restype = C.c_int
+        L.shc_put.argtypes = [C.POINTER(shq_table), vp, vp, C.c_int64, vp, vp, vp]
+        L.shc_put.restype = C.c_int
         _lib = L
     return _lib
 

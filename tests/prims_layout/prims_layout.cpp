@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdio.h>
 
+#include "../../siddhi_amd/csrc/sh_agg_seq.h"
 #include "../../siddhi_amd/csrc/sh_device.h"
 #include "../../siddhi_amd/csrc/sh_having.h"
 
@@ -49,5 +50,20 @@ int main() {
     OFF(shw_rows_out, ts);
     OFF(shw_rows_out, nulls);
     OFF(shw_rows_out, key);
+    SZ(sha_col);
+    OFF(sha_col, col);
+    OFF(sha_col, kind);
+    OFF(sha_col, arg_type);
+    OFF(sha_col, pad);
+    SZ(sha_desc);
+    OFF(sha_desc, n_cols);
+    OFF(sha_desc, pad);
+    OFF(sha_desc, c);
+    SZ(shq_table);
+    OFF(shq_table, keys);
+    OFF(shq_table, state);
+    OFF(shq_table, cap);
+    OFF(shq_table, n_cols);
+    OFF(shq_table, pad);
     return 0;
 }

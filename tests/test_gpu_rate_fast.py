@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from device_prims import shw_rows, shw_rows_out
+from device_prims import shq_table, shw_rows, shw_rows_out
 from having_fast_cases import PLAIN, assert_all_rows_equal
 from oracle_engine import OracleEngine, run_columns_oracle
 from rate_fast_cases import AGGREGATING, BY_NAME, R_F3, mix, rate_ref, with_rate
@@ -310,11 +310,6 @@ FILL = 0xA5
 EMPTY = 0xFFFFFFFFFFFFFFFF
 NONE, FIRST, LAST = 0, 1, 2
 BIG = 2**31 - 1
-
-
-class shq_table(C.Structure):
-    _fields_ = [("keys", C.c_void_p), ("state", C.c_void_p), ("cap", C.c_int64), ("n_cols", C.c_int32),
-                ("pad", C.c_int32)]
 
 
 def _prim_lib():
