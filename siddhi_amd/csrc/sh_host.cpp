@@ -719,7 +719,15 @@ static int upload_rules(sh_handle* h) {
 static int compile_nfa(sh_handle* h, const sh_app_desc* app) {
     nf_table* T = new nf_table();
     std::string err;
-    if (nf_lower(app, T, &err)) {
+    // a one-query app whose selector extras the row post-filter stage takes (the decision
+    // of the chain and rule engines): sh_run_device may run its rise-and-fall rungs with
+    // the stage behind them (s3q: the shape, when the query has it)
+    std::vector<shv_prog> hv;
+    std::vector<shl_rule> rl;
+    const int extras = app->n_queries == 1 && !h->hv_chain ? selector_extras(app, &hv, &rl) : 0;
+    const bool staged = extras && !(extras & SHX_GENERAL);
+    std::unique_ptr<nf_query> s3q(new nf_query());
+    if (nf_lower(app, T, &err, staged ? s3q.get() : nullptr)) {
         delete T;
         return fail(h, SH_E_UNSUPPORTED, err);
     }
@@ -729,6 +737,15 @@ static int compile_nfa(sh_handle* h, const sh_app_desc* app) {
     nf_set_caps(T, h->caps[0], h->caps[1], h->caps[2], h->caps[3], h->caps[4], h->caps[5]);
     h->T = T;
     h->mode = 1;
+    if (staged && s3q->s3) {
+        h->T3 = new nf_table(*T);
+        const size_t at = offsetof(nf_query, s3);
+        memcpy((char*)&h->T3->q[0] + at, (const char*)s3q.get() + at, sizeof(nf_query) - at);
+        h->hv_on = (extras & SHX_HAVING) != 0;
+        h->rl_on = (extras & SHX_RATE) != 0;
+        h->hv_progs.swap(hv);
+        h->rl_rules.swap(rl);
+    }
     int nout = 0;
     for (int q = 0; q < T->n_queries; q++) nout = std::max(nout, T->q[q].n_out);
     h->n_out = nout;
@@ -850,6 +867,10 @@ int sh_compile(const sh_app_desc* app, sh_handle** out) {
         h->n_err.set_view(h->n_ctl.as<uint8_t>() + 8, 8);
         h->n_sev_ctr.set_view(h->n_ctl.as<uint8_t>() + 16, 64);
         hipMemcpy(h->d_T.p, h->T, sizeof(nf_table), hipMemcpyHostToDevice);
+        if (h->T3) {
+            if (h->d_T3.ensure(sizeof(nf_table))) return fail(h, SH_E_OOM, "hipMalloc failed");
+            hipMemcpy(h->d_T3.p, h->T3, sizeof(nf_table), hipMemcpyHostToDevice);
+        }
     }
     if (h->has_rules && upload_rules(h)) return SH_E_OOM;
     if (h->hv_on) {
@@ -925,7 +946,7 @@ void sh_destroy(sh_handle* h) {
                            &h->n_ctr, &h->n_err, &h->n_cand, &h->n_sel, &h->n_bid, &h->w_oq,
                            &h->rd_rules, &h->rd_ixval, &h->rd_ixstart, &h->rd_ixrule, &h->rd_free, &h->rd_tab, &h->rd_img,
                            &h->r_tsr, &h->v_ts32, &h->v_sts32, &h->v_mid_ts32,
-                           &h->n_ctl,
+                           &h->n_ctl, &h->d_T3,
                            &h->r_rec, &h->r_keys, &h->r_g, &h->r_sk, &h->r_sv, &h->r_hist, &h->r_scan, &h->r_run};
         for (DevBuf* b : nbufs) b->release();
         for (auto& R : h->rc) {
@@ -956,6 +977,7 @@ void sh_destroy(sh_handle* h) {
         hipStreamDestroy(h->own_stream);
     }
     delete h->T;
+    delete h->T3;
     delete h;
 }
 
@@ -1488,7 +1510,7 @@ static int run_general(sh_handle* h, sh_device_run* run, bool rules_seq) {
     if (h->T->has_absent) return fail(h, SH_E_UNSUPPORTED, "sh_run_device: absent states need sh_push_batch");
     const int32_t nkeys = h->partitioned ? std::max(1, run->n_keys) : 1;
     if (nf_ensure_keys(h, nkeys)) return fail(h, SH_E_OOM, "key state");
-    const nf_query& Q0 = h->T->q[0];
+    const nf_query& Q0 = nf_bulk_table(h)->q[0];
     const bool aggp = h->T->n_queries == 1 && Q0.s3 && Q0.contains_agg;
     if (aggp && !run->d_out_seq) {
         if (h->a_seq.ensure((size_t)std::max<int64_t>(1, run->out_capacity) * 8))
@@ -1630,8 +1652,10 @@ static int run_chain(sh_handle* h, sh_device_run* run, int32_t nkeys) {
     return rc != 1 ? rc : rung_batch(h, run, nkeys);
 }
 
-// the engines of one sh_run_device call; *general: the general engine's rows stand
-// (its selector applied any `having`)
+// the engines of one sh_run_device call; *general: the rows that stand are k_nfa_run's
+// (its selector applied any `having` and event limiter: the row post-filter stage must
+// not apply them again), not those of a rise-and-fall rung of run_general (which knows
+// neither: the stage must)
 static int run_engines(sh_handle* h, sh_device_run* run, bool* general) {
     bool rules_seq = false;  // a rule set's aggregates left the post-pass for the general engine
     if (h->has_rules && (h->mode == 2 || !getenv("SH_DISABLE_RULES"))) {
@@ -1640,8 +1664,11 @@ static int run_engines(sh_handle* h, sh_device_run* run, bool* general) {
         rules_seq = true;
     }
     if (h->mode == 1 && !h->hv_chain) {
-        *general = true;
-        return run_general(h, run, rules_seq);
+        const int rc = run_general(h, run, rules_seq);
+        // (run_s3b clears s3b_last and every launch of nf_process sets seq3_last: after a
+        // second pass on k_nfa_run -- aggregates not exact in parallel -- both are 0)
+        *general = !(h->s3b_last || h->seq3_last);
+        return rc;
     }
     // the chain mode, from fresh per-key state
     const int32_t nkeys = h->partitioned ? std::max(1, run->n_keys) : 1;
@@ -1944,7 +1971,8 @@ int shx_host_profile(sh_handle* h, double* ms, int64_t* n, int cap) {
     return SH_HP_N;
 }
 // 1: the compiled app has the rise-and-fall sequence shape (no device needed)
-int shx_seq3_shape(sh_handle* h) { return h && h->T && h->T->n_queries == 1 && h->T->q[0].s3 ? 1 : 0; }
+// (also with a `having` / event limiter that the row post-filter stage applies behind it)
+int shx_seq3_shape(sh_handle* h) { return h && h->T && h->T->n_queries == 1 && nf_bulk_table(h)->q[0].s3 ? 1 : 0; }
 
 // compile-only check of the bucketed matcher shb_match (no device needed)
 int shx_bucket_compile(sh_handle* h, char* buf, int64_t len) {

@@ -1403,9 +1403,8 @@ int run_s3b(sh_handle* h, sh_device_run* run, int32_t nkeys) {
     const bool off = getenv("SH_DISABLE_S3B") != nullptr || getenv("SH_NO_SEQ3") != nullptr;  // (per call: tests A/B it)
     h->s3b_last = 0;
     h->bk_emit_last = 0;
-    if (off || !h->partitioned || h->T->n_queries != 1 || !h->T->q[0].s3 || nkeys < 1024 || run->n < SHB_TILE)
-        return 1;
-    const nf_query& Q = h->T->q[0];
+    const nf_query& Q = nf_bulk_table(h)->q[0];
+    if (off || !h->partitioned || h->T->n_queries != 1 || !Q.s3 || nkeys < 1024 || run->n < SHB_TILE) return 1;
     const int kb = std::max(0, bits_for((uint64_t)(nkeys - 1)) - 8);
     if (kb > 12 || Q.contains_agg) return 1;
     // every operand and select value: one 4-byte attribute A (no null masks on this path)

@@ -264,6 +264,13 @@ struct sh_handle {
     // ---- general engine (sh_nfa.h): mode 1
     int mode = 0;                 // 0: chain / window engines, 1: general NFA engine
     nf_table* T = nullptr;        // host copy of the NFA table
+    // a one-query rise-and-fall app with a `having` / event limiter that the row post-filter
+    // stage takes (compile_nfa): T as compiled with query 0's s3 fields set, and its device
+    // copy, read by sh_run_device's rungs (run_s3b, k_seq3 / k_seq3s) alone. T itself, which
+    // streaming, snapshot images and the fingerprint read, is the table of the app lowered
+    // without that stage. (Capacities grown later reach T only: those rungs keep no key blocks)
+    nf_table* T3 = nullptr;
+    DevBuf d_T3;
     DevBuf d_T, d_T_old, d_ncols, n_kstate, n_kstate2, n_save, n_recs, n_ctr, n_err, n_cand, n_sel, n_bid;
     // pinned staging of the streaming path: pin_in = one send() call's uploads,
     // pin_rd = small read-backs + the nf_cols image, pin_out = placed rows
@@ -503,6 +510,8 @@ struct NfOpts {                // nf_process's optional arguments
     const uint32_t* gidx = nullptr;
     int64_t n_idx = 0;
 };
+// the table sh_run_device's rise-and-fall rungs read: T3 where the handle has one
+inline const nf_table* nf_bulk_table(const sh_handle* h) { return h->T3 ? h->T3 : h->T; }
 bool nf_takes_seq3(const sh_handle* h);  // a single rise-and-fall query and no SH_NO_SEQ3 (read per call)
 int nf_process(sh_handle* h, const shd_batch& B, int32_t nkeys, const nf_cols& cols_in, uint64_t* d_seq,
                int64_t* d_vals, int64_t cap, int64_t* n_rows, const NfOpts& o = NfOpts());

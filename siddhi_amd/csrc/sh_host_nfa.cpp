@@ -658,7 +658,9 @@ static int nf_place(sh_handle* h, int64_t n_idx, int64_t* rows_out, uint64_t* d_
 }
 
 // a fresh run of this app takes the rise-and-fall engine k_seq3 (SH_NO_SEQ3: read per call)
-bool nf_takes_seq3(const sh_handle* h) { return h->T->n_queries == 1 && h->T->q[0].s3 && !getenv("SH_NO_SEQ3"); }
+bool nf_takes_seq3(const sh_handle* h) {
+    return h->T->n_queries == 1 && nf_bulk_table(h)->q[0].s3 && !getenv("SH_NO_SEQ3");
+}
 
 // one or more send() calls resident on the device, processed by k_nfa_run
 
@@ -734,7 +736,7 @@ int nf_process(sh_handle* h, const shd_batch& B, int32_t nkeys, const nf_cols& c
     // (4 bytes, no null mask), read from its key-ordered copy
     const void* s3_col = nullptr;
     if (s3_shape && sorted_cols) {
-        const nf_query& Q = h->T->q[0];
+        const nf_query& Q = nf_bulk_table(h)->q[0];
         const int A = Q.s3_a2, ty = Q.s3_t2;
         bool ok = (ty == SH_T_FLOAT || ty == SH_T_INT) && A >= 0 && A < (int)h->stream_types[0].size() &&
                   type_width(h->stream_types[0][A]) == 4 && Q.s3_a3 == A && Q.s3_e1a == A && Q.s3_la == A &&
@@ -748,7 +750,7 @@ int nf_process(sh_handle* h, const shd_batch& B, int32_t nkeys, const nf_cols& c
     // its records in the compact form (SH_S3_COMPACT=0: the generic records, for A/B)
     const bool s3_compact_on = !(getenv("SH_S3_COMPACT") && getenv("SH_S3_COMPACT")[0] == '0');
     h->s3_compact = s3_col && d_seq && s3_compact_on;
-    h->s3_type = h->T->q[0].s3_t2;
+    h->s3_type = (s3_shape ? nf_bulk_table(h) : h->T)->q[0].s3_t2;
     h->s3_seq_base = B.seq_base;
     // sum / avg / count in the kernel's lanes (each key's matches in trigger order: the
     // reference's own additions), when every aggregate is one of those and the record fits
@@ -844,8 +846,10 @@ int nf_launch(sh_handle* h, NfLaunch& L) {
     // the rise-and-fall sequence engine: fresh single-query runs of that shape
     h->seq3_last = L.s3_shape ? 1 : 0;
     if (L.s3_shape) {
-        if (nfd_seq3(h->d_T.as<nf_table>(), h->d_ncols.as<nf_cols>(), &L.E, L.n, L.seg_list, L.nseg, L.skeys,
-                     L.nkeys, L.max_seg, &em, st, L.s3_col, h->s3_compact ? 1 : 0, h->s3_agg ? 1 : 0, h->s3_rw))
+        // (the device copy of nf_bulk_table)
+        const nf_table* dT3 = (h->T3 ? h->d_T3 : h->d_T).as<nf_table>();
+        if (nfd_seq3(dT3, h->d_ncols.as<nf_cols>(), &L.E, L.n, L.seg_list, L.nseg, L.skeys, L.nkeys, L.max_seg, &em, st,
+                     L.s3_col, h->s3_compact ? 1 : 0, h->s3_agg ? 1 : 0, h->s3_rw))
             return fail(h, SH_E_HIP, "k_seq3 launch failed");
     } else if (nfd_run(h->d_T.as<nf_table>(), h->d_ncols.as<nf_cols>(), h->n_kstate.as<uint64_t>(), &L.E, L.n,
                        L.seg_list, L.nseg, L.skeys, L.nkeys, L.max_seg, h->tick, h->clock, &em, st))

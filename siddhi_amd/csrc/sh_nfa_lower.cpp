@@ -57,6 +57,7 @@ struct QueryLowering {
     const sh_query_desc* q;
     nf_table* T;
     nf_query* Q;
+    nf_query* S3 = nullptr;  // where the rise-and-fall shape of a query with selector extras goes (nf_lower)
     std::string err;
     std::vector<LProc> procs;
     std::vector<std::unique_ptr<LInner>> inners;
@@ -398,8 +399,9 @@ struct QueryLowering {
     // of the shared StateEvent before the count state sees it and drops it
     // (CountPreStateProcessor.java:60-68), and `every` re-arms e1 at every event.
     // Per key this is one partial (e1, last e2) — k_seq3 (sh_nfa.hip) runs it.
-    void detect_seq3() {
-        Q->s3 = 0;
+    // Writes the s3 fields of *D alone (the query's own entry, or the bulk-only copy).
+    void detect_seq3(nf_query* D) {
+        D->s3 = 0;
         if (q->state_type != SH_SEQUENCE || q->within_ms >= 0 || q->n_slots != 3 || q->n_outputs < 1) return;
         // flatten the NEXT chain
         std::vector<int> chain;
@@ -467,9 +469,9 @@ struct QueryLowering {
             // sum / avg / count of a plain attribute: the engine writes the argument,
             // the post-pass over the ordered rows forms the running value (sh_agg.hip)
             if (oa.agg == SH_AGG_COUNT && oa.expr < 0) {
-                Q->s3_out_slot[o] = 2;
-                Q->s3_out_attr[o] = 0;
-                Q->s3_out_type[o] = (int8_t)app->streams[c3.stream].attr_types[0];
+                D->s3_out_slot[o] = 2;
+                D->s3_out_attr[o] = 0;
+                D->s3_out_type[o] = (int8_t)app->streams[c3.stream].attr_types[0];
                 continue;
             }
             // (max / min too: k_seq3s keeps only sum / avg / count in its lanes, so
@@ -485,23 +487,23 @@ struct QueryLowering {
             if ((oa.agg == SH_AGG_MAX || oa.agg == SH_AGG_MIN) && ty != SH_T_INT && ty != SH_T_LONG && ty != SH_T_FLOAT &&
                 ty != SH_T_DOUBLE)
                 return;
-            Q->s3_out_slot[o] = (int8_t)x.slot;
-            Q->s3_out_attr[o] = (int8_t)at;
-            Q->s3_out_type[o] = (int8_t)ty;
+            D->s3_out_slot[o] = (int8_t)x.slot;
+            D->s3_out_attr[o] = (int8_t)at;
+            D->s3_out_type[o] = (int8_t)ty;
         }
-        Q->s3_op2 = (int8_t)op2;
-        Q->s3_dom2 = (int8_t)dom_for(op2, t2, e1t);
-        Q->s3_a2 = (int8_t)a2;
-        Q->s3_t2 = (int8_t)t2;
-        Q->s3_e1a = (int8_t)e1a;
-        Q->s3_e1t = (int8_t)e1t;
-        Q->s3_op3 = (int8_t)op3;
-        Q->s3_dom3 = (int8_t)dom_for(op3, t3, lt);
-        Q->s3_a3 = (int8_t)a3;
-        Q->s3_t3 = (int8_t)t3;
-        Q->s3_la = (int8_t)la;
-        Q->s3_lt = (int8_t)lt;
-        Q->s3 = 1;
+        D->s3_op2 = (int8_t)op2;
+        D->s3_dom2 = (int8_t)dom_for(op2, t2, e1t);
+        D->s3_a2 = (int8_t)a2;
+        D->s3_t2 = (int8_t)t2;
+        D->s3_e1a = (int8_t)e1a;
+        D->s3_e1t = (int8_t)e1t;
+        D->s3_op3 = (int8_t)op3;
+        D->s3_dom3 = (int8_t)dom_for(op3, t3, lt);
+        D->s3_a3 = (int8_t)a3;
+        D->s3_t3 = (int8_t)t3;
+        D->s3_la = (int8_t)la;
+        D->s3_lt = (int8_t)lt;
+        D->s3 = 1;
     }
 
     bool run() {
@@ -606,9 +608,14 @@ struct QueryLowering {
             err = "device engine: at most 16 output attributes";
             return false;
         }
-        // k_seq3 emits without a selector pass
+        // k_seq3 emits without a selector pass: a query with none of these, or -- for
+        // sh_run_device alone, in *S3 -- one whose `having` / event limiter the caller's
+        // row post-filter stage applies behind it. The table's own entry stays as it
+        // lowers without that stage: k_nfa_run's selector applies both
         if (q->having < 0 && q->n_order == 0 && q->limit < 0 && q->offset < 0 && q->rate_kind == SH_RATE_NONE)
-            detect_seq3();
+            detect_seq3(Q);
+        else if (S3)
+            detect_seq3(S3);
         Q->n_out = q->n_outputs;
         for (int o = 0; o < q->n_outputs; o++) {
             const sh_output_attr& oa = q->outputs[o];
@@ -711,8 +718,9 @@ struct QueryLowering {
 
 }  // namespace
 
-int nf_lower(const sh_app_desc* app, nf_table* T, std::string* err) {
+int nf_lower(const sh_app_desc* app, nf_table* T, std::string* err, nf_query* bulk_s3) {
     memset(T, 0, sizeof(*T));
+    if (bulk_s3) memset(bulk_s3, 0, sizeof(*bulk_s3));
     if (app->n_queries < 1 || app->n_queries > NF_MAX_QUERIES) {
         *err = "device engine: 1..16 queries per app";
         return -1;
@@ -768,6 +776,7 @@ int nf_lower(const sh_app_desc* app, nf_table* T, std::string* err) {
         L.q = &app->queries[i];
         L.T = T;
         L.Q = &T->q[i];
+        L.S3 = app->n_queries == 1 ? bulk_s3 : nullptr;
         if (!L.run()) {
             *err = "query " + std::to_string(i) + ": " + L.err;
             return -1;
