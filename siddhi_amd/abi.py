@@ -180,6 +180,12 @@ def bind_product(lib):
     lib.shx_seq3_status.restype = C.c_int
     lib.shx_agg_status.argtypes = [C.c_void_p]
     lib.shx_agg_status.restype = C.c_int
+    lib.shx_group_status.argtypes = [C.c_void_p]
+    lib.shx_group_status.restype = C.c_int
+    lib.shx_group_compiled.argtypes = [C.c_void_p]
+    lib.shx_group_compiled.restype = C.c_int
+    lib.shx_agg_post_ms.argtypes = [C.c_void_p]
+    lib.shx_agg_post_ms.restype = C.c_double
     lib.shx_having_status.argtypes = [C.c_void_p]
     lib.shx_having_status.restype = C.c_int
     lib.shx_having_rows.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]

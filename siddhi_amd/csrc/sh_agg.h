@@ -33,6 +33,14 @@ int64_t sha_scratch_bytes(int64_t m, int n_cols);
 int sha_running(const uint64_t* d_seq, int64_t* d_vals, int32_t n_out, int64_t m, const int32_t* d_query,
                 int32_t n_query, const int32_t* d_keys, int32_t n_keys, uint64_t seq_base, const sha_desc* D,
                 void* d_scratch, void* stream);
+// The same under `group by` (sh_group.h): a segment is (query, partition key, the
+// row's group values as G lists them per query; a query G gives no attributes keeps
+// (query, key)). G is the host's descriptor. Same answers as sha_running.
+struct sha_groups;
+int64_t sha_grouped_scratch_bytes(int64_t m, int n_cols);
+int sha_running_grouped(const uint64_t* d_seq, int64_t* d_vals, int32_t n_out, int64_t m, const int32_t* d_query,
+                        int32_t n_query, const int32_t* d_keys, int32_t n_keys, uint64_t seq_base, const sha_desc* D,
+                        const struct sha_groups* G, void* d_scratch, void* stream);
 #ifdef __cplusplus
 }
 #endif

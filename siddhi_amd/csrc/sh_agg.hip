@@ -40,7 +40,9 @@
 // aggregates) -> k_sha_out (carry-in, exactness check, double conversion)
 // -> k_sha_scatter (every column back into its row, one row write). A max / min
 // column takes k_shm_tile -> k_shm_carry -> k_shm_out between the same gather and
-// scatter.
+// scatter. Under `group by` (sha_running_grouped) the segment ids and the sorted order
+// come from sh_group.hip instead -- a segment is (query, key, group values) -- and
+// everything from k_sha_gather on is the same.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -50,6 +52,7 @@
 #include "sh_agg.h"
 #include "sh_agg_seq.h"
 #include "sh_device.h"
+#include "sh_group.h"
 #include "sh_wave.h"
 
 #define SHA_TPB 256
@@ -623,14 +626,18 @@ extern "C" int64_t sha_scratch_bytes(int64_t m, int n_cols) {
 
 static int sha_ok() { return hipGetLastError() == hipSuccess ? 0 : -3; }
 
-extern "C" int sha_running(const uint64_t* d_seq, int64_t* d_vals, int32_t n_out, int64_t m, const int32_t* d_query,
-                           int32_t n_query, const int32_t* d_keys, int32_t n_keys, uint64_t seq_base,
-                           const sha_desc* D, void* d_scratch, void* stream) {
-    if (m <= 0 || D->n_cols == 0) return 0;
-    if (m >= ((int64_t)1 << 32) || n_out < 1 || !d_seq || !d_vals || !d_scratch) return -1;
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t nseg = (int64_t)(n_query < 1 ? 1 : n_query) * (n_keys < 1 ? 1 : n_keys);
-    if (nseg > ((int64_t)1 << 32)) return -1;
+// the workspace of one sha_running call (sha_scratch_bytes)
+struct sha_ws {
+    uint32_t *seg, *idx, *kb0, *kb1, *vb0, *vb1;
+    sha_i128* sv;
+    int64_t* sc;
+    sha_el* tiles;
+    uint32_t *fh, *hist, *stmp;
+    int32_t* range;
+    int64_t* scol;
+};
+
+static uint8_t* sha_carve(void* d_scratch, int64_t m, int n_cols, sha_ws* W) {
     const int64_t nt = (m + SHA_TILE - 1) / SHA_TILE;
     const int64_t rt = (m + 4095) / 4096;
     uint8_t* p = (uint8_t*)d_scratch;
@@ -639,39 +646,54 @@ extern "C" int sha_running(const uint64_t* d_seq, int64_t* d_vals, int32_t n_out
         p += (bytes + 255) & ~(int64_t)255;
         return (void*)r;
     };
-    uint32_t* seg = (uint32_t*)take(m * 4);
-    uint32_t* idx = (uint32_t*)take(m * 4);
-    uint32_t* kb0 = (uint32_t*)take(m * 4);
-    uint32_t* kb1 = (uint32_t*)take(m * 4);
-    uint32_t* vb0 = (uint32_t*)take(m * 4);
-    uint32_t* vb1 = (uint32_t*)take(m * 4);
-    sha_i128* sv = (sha_i128*)take(m * 16);
-    int64_t* sc = (int64_t*)take(m * 8);
-    sha_el* tiles = (sha_el*)take(nt * (int64_t)sizeof(sha_el));
-    uint32_t* fh = (uint32_t*)take(nt * 4);
-    uint32_t* hist = (uint32_t*)take(256 * rt * 4);
-    uint32_t* stmp = (uint32_t*)take((int64_t)shd_scan_tmp_words(256 * rt) * 4);
-    int32_t* range = (int32_t*)take(4 * 3 * SHA_MAX_COLS + 64);
-    int64_t* scol = (int64_t*)take((int64_t)D->n_cols * m * 8);
+    W->seg = (uint32_t*)take(m * 4);
+    W->idx = (uint32_t*)take(m * 4);
+    W->kb0 = (uint32_t*)take(m * 4);
+    W->kb1 = (uint32_t*)take(m * 4);
+    W->vb0 = (uint32_t*)take(m * 4);
+    W->vb1 = (uint32_t*)take(m * 4);
+    W->sv = (sha_i128*)take(m * 16);
+    W->sc = (int64_t*)take(m * 8);
+    W->tiles = (sha_el*)take(nt * (int64_t)sizeof(sha_el));
+    W->fh = (uint32_t*)take(nt * 4);
+    W->hist = (uint32_t*)take(256 * rt * 4);
+    W->stmp = (uint32_t*)take((int64_t)shd_scan_tmp_words(256 * rt) * 4);
+    W->range = (int32_t*)take(4 * 3 * SHA_MAX_COLS + 64);
+    W->scol = (int64_t*)take((int64_t)n_cols * m * 8);
+    return p;
+}
+
+// the exponent ranges' start values, then k_sha_prep: segment ids, row indices, ranges
+static int sha_prep(const uint64_t* d_seq, const int64_t* d_vals, int32_t n_out, int64_t m, const int32_t* d_query,
+                    const int32_t* d_keys, int32_t n_keys, uint64_t seq_base, const sha_desc* D, const sha_ws& W,
+                    hipStream_t st) {
     int32_t h_range[3 * SHA_MAX_COLS];
     for (int k = 0; k < SHA_MAX_COLS; k++) {
         h_range[3 * k] = 1 << 30;
         h_range[3 * k + 1] = -(1 << 30);
         h_range[3 * k + 2] = 0;
     }
-    hipMemcpyAsync(range, h_range, sizeof(h_range), hipMemcpyHostToDevice, st);
-    hipMemsetAsync(range + 3 * SHA_MAX_COLS, 0, 4, st);
+    hipMemcpyAsync(W.range, h_range, sizeof(h_range), hipMemcpyHostToDevice, st);
+    hipMemsetAsync(W.range + 3 * SHA_MAX_COLS, 0, 4, st);
     const unsigned g = (unsigned)((m + SHA_TPB - 1) / SHA_TPB);
-    hipLaunchKernelGGL(k_sha_prep, dim3((unsigned)std::min<int64_t>(g, 2048)), dim3(SHA_TPB), 0, st, d_seq, (const int64_t*)d_vals, n_out, m, d_query,
-                       d_keys, n_keys, seq_base, *D, seg, idx, range);
-    if (sha_ok()) return -3;
-    int bits = 0;
-    while (bits < 32 && ((int64_t)1 << bits) < nseg) bits++;
-    const uint32_t* sseg = seg;
-    const uint32_t* sidx = idx;
-    uint32_t* kbuf[2] = {kb0, kb1};
-    uint32_t* vbuf[2] = {vb0, vb1};
-    if (bits > 0 && shd_sort_pairs(seg, idx, m, bits, kbuf, vbuf, hist, stmp, stream, &sseg, &sidx)) return -3;
+    hipLaunchKernelGGL(k_sha_prep, dim3((unsigned)std::min<int64_t>(g, 2048)), dim3(SHA_TPB), 0, st, d_seq, d_vals, n_out, m, d_query,
+                       d_keys, n_keys, seq_base, *D, W.seg, W.idx, W.range);
+    return sha_ok();
+}
+
+// from the sorted segment ids sseg and the sorted order sidx on: gather, the scans per
+// column, the exactness verdict, scatter (what a segment is does not matter here)
+static int sha_tail(int64_t* d_vals, int32_t n_out, int64_t m, const sha_desc* D, const sha_ws& W,
+                    const uint32_t* sseg, const uint32_t* sidx, hipStream_t st) {
+    const int64_t nt = (m + SHA_TILE - 1) / SHA_TILE;
+    const unsigned g = (unsigned)((m + SHA_TPB - 1) / SHA_TPB);
+    sha_i128* sv = W.sv;
+    int64_t* sc = W.sc;
+    sha_el* tiles = W.tiles;
+    uint32_t* fh = W.fh;
+    int32_t* range = W.range;
+    int64_t* scol = W.scol;
+    int32_t h_range[3 * SHA_MAX_COLS];
     hipLaunchKernelGGL(k_sha_gather, dim3(g), dim3(SHA_TPB), 0, st, (const int64_t*)d_vals, n_out, sidx, m, *D, scol);
     hipMemcpyAsync(h_range, range, sizeof(h_range), hipMemcpyDeviceToHost, st);
     if (hipStreamSynchronize(st) != hipSuccess) return -3;
@@ -716,6 +738,55 @@ extern "C" int sha_running(const uint64_t* d_seq, int64_t* d_vals, int32_t n_out
                        (const int64_t*)scol);
     if (sha_ok()) return -3;
     return 0;
+}
+
+extern "C" int sha_running(const uint64_t* d_seq, int64_t* d_vals, int32_t n_out, int64_t m, const int32_t* d_query,
+                           int32_t n_query, const int32_t* d_keys, int32_t n_keys, uint64_t seq_base,
+                           const sha_desc* D, void* d_scratch, void* stream) {
+    if (m <= 0 || D->n_cols == 0) return 0;
+    if (m >= ((int64_t)1 << 32) || n_out < 1 || !d_seq || !d_vals || !d_scratch) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t nseg = (int64_t)(n_query < 1 ? 1 : n_query) * (n_keys < 1 ? 1 : n_keys);
+    if (nseg > ((int64_t)1 << 32)) return -1;
+    sha_ws W;
+    sha_carve(d_scratch, m, D->n_cols, &W);
+    if (sha_prep(d_seq, (const int64_t*)d_vals, n_out, m, d_query, d_keys, n_keys, seq_base, D, W, st)) return -3;
+    int bits = 0;
+    while (bits < 32 && ((int64_t)1 << bits) < nseg) bits++;
+    const uint32_t* sseg = W.seg;
+    const uint32_t* sidx = W.idx;
+    uint32_t* kbuf[2] = {W.kb0, W.kb1};
+    uint32_t* vbuf[2] = {W.vb0, W.vb1};
+    if (bits > 0 && shd_sort_pairs(W.seg, W.idx, m, bits, kbuf, vbuf, W.hist, W.stmp, stream, &sseg, &sidx)) return -3;
+    return sha_tail(d_vals, n_out, m, D, W, sseg, sidx, st);
+}
+
+// `group by` (sh_group.h): the same pass over the segments (query, key, group values).
+// The workspace is sha_running's followed by the segment pass's.
+extern "C" int64_t sha_grouped_scratch_bytes(int64_t m, int n_cols) {
+    return ((sha_scratch_bytes(m, n_cols) + 255) & ~(int64_t)255) + shg_scratch_bytes(m);
+}
+
+extern "C" int sha_running_grouped(const uint64_t* d_seq, int64_t* d_vals, int32_t n_out, int64_t m,
+                                   const int32_t* d_query, int32_t n_query, const int32_t* d_keys, int32_t n_keys,
+                                   uint64_t seq_base, const sha_desc* D, const sha_groups* G, void* d_scratch,
+                                   void* stream) {
+    if (m <= 0 || D->n_cols == 0) return 0;
+    if (m >= ((int64_t)1 << 32) || n_out < 1 || !d_seq || !d_vals || !d_scratch || !shg_valid(G, n_out)) return -1;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t nseg = (int64_t)(n_query < 1 ? 1 : n_query) * (n_keys < 1 ? 1 : n_keys);
+    if (nseg > ((int64_t)1 << 32)) return -1;
+    sha_ws W;
+    sha_carve(d_scratch, m, D->n_cols, &W);
+    uint8_t* gws = (uint8_t*)d_scratch + ((sha_scratch_bytes(m, D->n_cols) + 255) & ~(int64_t)255);
+    // (k_sha_prep for the exponent ranges; its segment ids are the ungrouped ones and unused)
+    if (sha_prep(d_seq, (const int64_t*)d_vals, n_out, m, d_query, d_keys, n_keys, seq_base, D, W, st)) return -3;
+    const uint32_t* sseg = nullptr;
+    const uint32_t* sidx = nullptr;
+    const int rc = shg_segments(d_seq, (const int64_t*)d_vals, n_out, m, d_query, n_query, d_keys, n_keys, seq_base, G,
+                                gws, stream, &sseg, &sidx);
+    if (rc) return rc;
+    return sha_tail(d_vals, n_out, m, D, W, sseg, sidx, st);
 }
 
 // ---------------------------------------------------------------- carried, sequential pass

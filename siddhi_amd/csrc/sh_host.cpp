@@ -397,15 +397,62 @@ static int lower_chain(sh_handle* h, const sh_app_desc* app, int qi, shp_program
 // (sh_rate.h; `all` moves rows to their chunk's N-th instead of dropping them): the
 // fast engines take the app, with the device row filter (SHX_HAVING: its programs in
 // *progs, one per query) and the limiter pass (SHX_RATE: its rules in *rules, one per
-// query) behind them. 0: none of these
-enum { SHX_HAVING = 1, SHX_RATE = 2, SHX_GENERAL = 4 };
-static int selector_extras(const sh_app_desc* app, std::vector<shv_prog>* progs, std::vector<shl_rule>* rules) {
+// query) behind them. `group by` only widens what keys the aggregators' states: when
+// every group-by expression is also a plain output of the select (the same variable: no
+// aggregator, no arithmetic), the group values are in the row and the aggregate
+// post-pass takes (query, key, group values) for its segments (SHX_GROUP: the row
+// positions and types in *groups, sh_group.h; a query without an aggregator, where the
+// clause has no effect, lists none). A set beyond the general engine's query table
+// never groups. 0: none of these
+enum { SHX_HAVING = 1, SHX_RATE = 2, SHX_GENERAL = 4, SHX_GROUP = 8 };
+static bool group_same_var(const sh_expr& a, const sh_expr& b) {
+    // (a pattern state without a count holds one event: index 0 is the current one)
+    auto first = [](const sh_expr& x) { return x.chain == 0 || x.chain == SH_CHAIN_CURRENT; };
+    return a.op == SH_OP_VAR && b.op == SH_OP_VAR && a.slot == b.slot && a.attr == b.attr && a.type == b.type &&
+           (a.chain == b.chain || (first(a) && first(b)));
+}
+static int selector_extras(const sh_app_desc* app, std::vector<shv_prog>* progs, std::vector<shl_rule>* rules,
+                           sha_groups* groups) {
     int extras = 0;
     if (progs) progs->assign((size_t)std::max(0, app->n_queries), shv_prog{});
     if (rules) rules->assign((size_t)std::max(0, app->n_queries), shl_rule{SH_RATE_NONE, 0});
+    if (groups) memset(groups, 0, sizeof(*groups));
+    if (groups) groups->n_query = std::max(1, std::min(app->n_queries, (int32_t)SHG_MAX_QUERIES));
     for (int32_t q = 0; q < app->n_queries; q++) {
         const sh_query_desc& d = app->queries[q];
-        if (d.n_order > 0 || d.limit >= 0 || d.offset >= 0 || d.n_group > 0) return SHX_GENERAL;
+        if (d.n_order > 0 || d.limit >= 0 || d.offset >= 0) return SHX_GENERAL;
+        bool aggregates = false;
+        for (int32_t o = 0; o < d.n_outputs; o++) aggregates |= d.outputs[o].agg != SH_AGG_NONE;
+        // every grouped query, with an aggregator or not, is the general engine's for a
+        // caller that asks for no layout (compile_nfa: the rise-and-fall rungs), under the
+        // switch and in a set beyond the query table (refused, as ever)
+        if (d.n_group > 0 &&
+            (!groups || getenv("SH_NO_GROUP_POST") || d.n_group > SH_MAX_GROUP || app->n_queries > SHG_MAX_QUERIES))
+            return SHX_GENERAL;
+        // without an aggregator the clause has no effect on the rows: SHX_GROUP with no
+        // attributes (bulk runs take the fast engines as without it; the handle still
+        // streams on the general engine, as every app with an extra here does)
+        if (d.n_group > 0 && !aggregates) extras |= SHX_GROUP;
+        if (d.n_group > 0 && aggregates) {
+            sha_group_q& g = groups->q[q];
+            for (int32_t i = 0; i < d.n_group; i++) {
+                const int32_t ge = d.group_expr[i];
+                if (ge < 0 || ge >= d.n_exprs) return SHX_GENERAL;
+                int32_t at = -1;
+                for (int32_t o = 0; o < d.n_outputs && at < 0; o++) {
+                    const sh_output_attr& oa = d.outputs[o];
+                    if (oa.agg == SH_AGG_NONE && oa.expr >= 0 && oa.expr < d.n_exprs &&
+                        group_same_var(d.exprs[ge], d.exprs[oa.expr]))
+                        at = o;
+                }
+                const int32_t t = d.exprs[ge].type;
+                if (at < 0 || t < SH_T_STRING || t > SH_T_BOOL) return SHX_GENERAL;
+                g.col[i] = at;
+                g.type[i] = t;
+            }
+            g.n = d.n_group;
+            extras |= SHX_GROUP;
+        }
         // a List output (SH_OP_MULTI_VAR) is built by the general engine's selector
         for (int32_t o = 0; o < d.n_outputs; o++)
             if (d.outputs[o].expr >= 0 && d.outputs[o].expr < d.n_exprs && d.exprs[d.outputs[o].expr].op == SH_OP_MULTI_VAR)
@@ -433,20 +480,23 @@ static int compile_chain(sh_handle* h, const sh_app_desc* app) {
     if (app->n_queries != 1) return fail(h, SH_E_UNSUPPORTED, "chain engine: one query per app");
     std::vector<shv_prog> hv;
     std::vector<shl_rule> rl;
-    const int extras = selector_extras(app, &hv, &rl);
+    sha_groups grp;
+    const int extras = selector_extras(app, &hv, &rl, &grp);
     if (extras & SHX_GENERAL)
         return fail(h, SH_E_UNSUPPORTED, "chain engine: order by / limit / a having over state-event attributes / "
-                                         "time limiters run on the general engine");
+                                         "time limiters / a group by outside the select run on the general engine");
     shp_program P;
     int rc = lower_chain(h, app, 0, P);
     if (rc) return rc;
     // an output-only `having` or an event limiter on a window-shaped query:
     // sh_push_batch stays on the general engine (whose selector applies them),
     // sh_run_device takes the chain mode's rungs with the device row filter and the
-    // limiter pass behind them (hv_chain, as has_rules does for a small rule set)
+    // limiter pass behind them (hv_chain, as has_rules does for a small rule set); a
+    // grouped select likewise, with the grouped post-pass forming its running values
+    // (a window-shaped aggregating query has agg_post set)
     if (extras && !P.window_ok)
-        return fail(h, SH_E_UNSUPPORTED, "chain engine: having / output rate limiting on a shape outside the window "
-                                         "engines runs on the general engine");
+        return fail(h, SH_E_UNSUPPORTED, "chain engine: having / output rate limiting / group by on a shape outside "
+                                         "the window engines runs on the general engine");
     h->prog = P;
     h->n_out = P.n_out;
     h->partitioned = app->queries[0].partition >= 0;
@@ -460,9 +510,12 @@ static int compile_chain(sh_handle* h, const sh_app_desc* app) {
         h->hv_chain = true;
         h->hv_on = (extras & SHX_HAVING) != 0;
         h->rl_on = (extras & SHX_RATE) != 0;
+        h->grp_on = (extras & SHX_GROUP) != 0 && grp.q[0].n > 0;
+        h->grp = grp;
         h->hv_progs.swap(hv);
         h->rl_rules.swap(rl);
-        return fail(h, SH_E_UNSUPPORTED, "chain engine: having / output rate limiting stream on the general engine");
+        return fail(h, SH_E_UNSUPPORTED, "chain engine: having / output rate limiting / group by stream on the "
+                                         "general engine");
     }
     return SH_OK;
 }
@@ -489,10 +542,16 @@ static int compile_rules(sh_handle* h, const sh_app_desc* app) {
         return fail(h, SH_E_UNSUPPORTED, "rule engine: two or more queries over one stream");
     std::vector<shv_prog> hv;
     std::vector<shl_rule> rl;
-    const int extras = selector_extras(app, &hv, &rl);
+    sha_groups grp;
+    const int extras = selector_extras(app, &hv, &rl, &grp);
     if (extras & SHX_GENERAL)
         return fail(h, SH_E_UNSUPPORTED, "rule engine: order by / limit / a having over state-event attributes / time "
-                                         "limiters run on the general engine");
+                                         "limiters / a group by outside the select run on the general engine");
+    // `group by`: one group layout for the whole set, as the aggregates have one
+    if (extras & SHX_GROUP)
+        for (int qi = 1; qi < app->n_queries; qi++)
+            if (memcmp(&grp.q[qi], &grp.q[0], sizeof(sha_group_q)))
+                return fail(h, SH_E_UNSUPPORTED, "rule engine: the queries group by different select positions");
     // `all every N` holds rows back: a set that only this engine can stream (beyond the
     // general engine's query table) would have to carry them between steps and in snapshots
     if (app->n_queries > NF_MAX_QUERIES)
@@ -600,6 +659,8 @@ static int compile_rules(sh_handle* h, const sh_app_desc* app) {
     h->has_rules = true;
     h->hv_on = (extras & SHX_HAVING) != 0;
     h->rl_on = (extras & SHX_RATE) != 0;
+    h->grp_on = (extras & SHX_GROUP) != 0 && h->r_aggp && grp.q[0].n > 0;
+    h->grp = grp;
     h->hv_progs.swap(hv);
     h->rl_rules.swap(rl);
     return SH_OK;
@@ -724,7 +785,8 @@ static int compile_nfa(sh_handle* h, const sh_app_desc* app) {
     // the stage behind them (s3q: the shape, when the query has it)
     std::vector<shv_prog> hv;
     std::vector<shl_rule> rl;
-    const int extras = app->n_queries == 1 && !h->hv_chain ? selector_extras(app, &hv, &rl) : 0;
+    // (no group layout asked for: a grouped select stays with k_nfa_run's selector here)
+    const int extras = app->n_queries == 1 && !h->hv_chain ? selector_extras(app, &hv, &rl, nullptr) : 0;
     const bool staged = extras && !(extras & SHX_GENERAL);
     std::unique_ptr<nf_query> s3q(new nf_query());
     if (nf_lower(app, T, &err, staged ? s3q.get() : nullptr)) {
@@ -837,7 +899,7 @@ int sh_compile(const sh_app_desc* app, sh_handle** out) {
         const bool rules = compile_rules(h, app) == SH_OK;
         const std::string rules_err = rules ? std::string() : h->err;
         rc = compile_nfa(h, app);
-        if (rc && h->hv_chain) h->hv_on = h->rl_on = h->hv_chain = false;
+        if (rc && h->hv_chain) h->hv_on = h->rl_on = h->grp_on = h->hv_chain = false;
         if (rc && rules) {
             // rule sets beyond the general engine's query table: bulk path only
             rc = SH_OK;
@@ -1603,18 +1665,29 @@ static int bucket_agg_modes(const sh_handle* h, const sh_device_run* run, bool a
 // columns), the window engine, the sequential engine. agg: under a select with
 // aggregators (agg_status in brackets) the bucketed engine's carries form the running
 // values themselves, and the post-pass (sh_agg.hip) forms them from raw rows of
-// arguments, 1 when its additions would round in parallel
-static int run_chain(sh_handle* h, sh_device_run* run, int32_t nkeys) {
+// arguments, 1 when its additions would round in parallel. Under `group by`
+// (h->grp_on) the carries are out -- they are per key -- so the bucketed engine only
+// writes arguments, the post-pass is the grouped one, and where the ladder would go on
+// to an engine that adds in sequence per key it answers *to_general: the general
+// engine, whose selector knows the clause
+static int run_chain(sh_handle* h, sh_device_run* run, int32_t nkeys, bool* to_general) {
     const shp_program& P = h->prog;
     const bool agg = P.agg_post != 0;
+    const bool grouped = h->grp_on;
     auto post = [&] { return agg_post(h, run, nkeys, nullptr, 1, P.out_agg, P.out_arg_type, P.n_out); };
+    auto last_rung = [&] {
+        if (!grouped) return rung_batch(h, run, nkeys);
+        *to_general = true;
+        return (int)SH_OK;
+    };
     BkAgg m[2] = {BK_AGG_ROWS, BK_AGG_ROWS};
     BkRun br;
     int rc;
     // 1. packed rows / typed columns straight from the bucketed engine when its
     // parallel carry takes the batch [5], or nothing
-    if (agg && P.window_ok && h->out_mode != SHB_OUT_RAW && !h->cols_rows && bucket_agg_modes(h, run, false, m) &&
-        m[0] == BK_AGG_PAR && (rc = run_bucket(h, run, nkeys, BK_AGG_PAR, &br)) != 1)
+    if (agg && !grouped && P.window_ok && h->out_mode != SHB_OUT_RAW && !h->cols_rows &&
+        bucket_agg_modes(h, run, false, m) && m[0] == BK_AGG_PAR &&
+        (rc = run_bucket(h, run, nkeys, BK_AGG_PAR, &br)) != 1)
         return rc;
     // 2. raw rows from here on, with sequence numbers for the post-pass
     if (agg && (rc = rows_for_cols(h, run))) return rc;
@@ -1627,7 +1700,7 @@ static int run_chain(sh_handle* h, sh_device_run* run, int32_t nkeys) {
     // once more in the next after the device refused the parallel carry
     rc = 1;
     if (P.window_ok) {
-        const int nm = agg ? bucket_agg_modes(h, run, false, m) : 1;
+        const int nm = agg && !grouped ? bucket_agg_modes(h, run, false, m) : 1;
         rc = run_bucket(h, run, nkeys, m[0], &br);
         if (rc == 1 && br.refused && nm > 1) rc = run_bucket(h, run, nkeys, m[1], &br);
     }
@@ -1636,12 +1709,12 @@ static int run_chain(sh_handle* h, sh_device_run* run, int32_t nkeys) {
         if ((rc = post()) <= 0) return rc;
         // 5. not exact [2]: the bucketed engine again, its sequential carry adding in
         // the reference's sequence [4]
-        if (bucket_agg_modes(h, run, true, m)) {
+        if (!grouped && bucket_agg_modes(h, run, true, m)) {
             rc = run_bucket(h, run, nkeys, m[0], &br);
             if (rc == SH_OK && br.carried != BK_AGG_ROWS) return SH_OK;
             if (rc != SH_OK && rc != 1) return rc;
         }
-        return rung_batch(h, run, nkeys);  // [2]
+        return last_rung();  // [2]
     }
     if (rc != 1) return rc;
     // 6. the window engine, on raw rows, and the post-pass of its rows [1]
@@ -1649,7 +1722,7 @@ static int run_chain(sh_handle* h, sh_device_run* run, int32_t nkeys) {
     rc = P.window_ok ? run_window(h, run, nkeys) : 1;
     if (agg && rc == SH_OK && (rc = post()) <= 0) return rc;
     // 7. the sequential engine: timestamps decrease inside a key, or not exact [2]
-    return rc != 1 ? rc : rung_batch(h, run, nkeys);
+    return rc != 1 ? rc : last_rung();
 }
 
 // the engines of one sh_run_device call; *general: the rows that stand are k_nfa_run's
@@ -1676,7 +1749,15 @@ static int run_engines(sh_handle* h, sh_device_run* run, bool* general) {
     hipMemsetAsync(h->d_kstate.p, 0, (size_t)nkeys * h->lay.key_bytes, h->stream);
     h->times = sh_kernel_times{};
     h->agg_last = 0;
-    return run_chain(h, run, nkeys);
+    bool to_general = false;
+    const int rc = run_chain(h, run, nkeys, &to_general);
+    if (!to_general) return rc;
+    // a grouped select whose additions would round in parallel (agg_status 2), or whose
+    // timestamps decrease inside a key: k_nfa_run, whose selector applies `group by`
+    // (and any `having` / limiter beside it) itself
+    h->bk_last = 0;
+    *general = true;
+    return run_general(h, run, h->agg_last == 2);
 }
 
 // The row post-filter stage. Under an output-only `having` (h->hv_on) or an event
@@ -1752,6 +1833,8 @@ static int run_device_impl(sh_handle* h, sh_device_run* run) {
     // wait for them)
     h->stream = (hipStream_t)run->stream;
     h->hv.last = h->rl.last = 0;
+    h->grp_last = 0;
+    h->agg_post_ms = 0.0;
     if (h->hv_on || h->rl_on) return run_device_post(h, run);
     bool general = false;
     return run_engines(h, run, &general);
@@ -1916,6 +1999,14 @@ int shx_seq3_status(sh_handle* h) { return h ? (h->s3b_last ? 2 : h->seq3_last) 
 // aggregators of the last sh_run_device: 0 none on a fast engine, 1 the post-pass
 // (sh_agg.hip) formed them, 2 it was not exact and a sequential engine ran
 int shx_agg_status(sh_handle* h) { return h ? h->agg_last : 0; }
+// 1: the grouped post-pass (sha_running_grouped) produced the last sh_run_device's rows
+int shx_group_status(sh_handle* h) { return h ? h->grp_last : 0; }
+// 1: the handle was compiled with a group layout (selector_extras: sh_run_device takes a
+// fast engine with the grouped post-pass behind it), 0: it does not group, or the
+// general engine's selector applies the clause. Needs no device
+int shx_group_compiled(sh_handle* h) { return h && h->grp_on ? 1 : 0; }
+// device time of the last run's aggregate post-pass (agg_post), ms
+double shx_agg_post_ms(sh_handle* h) { return h ? h->agg_post_ms : 0.0; }
 
 // `having` of the last sh_run_device or streaming step: 1 the device row filter
 // (sh_having.hip) applied it, 0 there is none or the general engine's selector did

@@ -1602,11 +1602,19 @@ int agg_post(sh_handle* h, sh_device_run* run, int32_t nkeys, const int32_t* d_q
             D.n_cols++;
         }
     if (D.n_cols == 0) return SH_OK;
-    if (h->a_scratch.ensure((size_t)sha_scratch_bytes(m, D.n_cols))) return fail(h, SH_E_OOM, "aggregate scratch");
+    // under `group by` (h->grp_on: a chain-mode query or a small rule set) the segments
+    // are (query, key, group values)
+    const bool grouped = h->grp_on;
+    if (h->a_scratch.ensure((size_t)(grouped ? sha_grouped_scratch_bytes(m, D.n_cols) : sha_scratch_bytes(m, D.n_cols))))
+        return fail(h, SH_E_OOM, "aggregate scratch");
     hipEventRecord(h->ev[4], h->stream);
-    const int rc = sha_running(run->d_out_seq, run->d_out_values, n_out, m, d_query, n_query,
-                               h->partitioned ? run->d_keys : nullptr, h->partitioned ? nkeys : 1, 0, &D,
-                               h->a_scratch.p, h->stream);
+    const int32_t* keys = h->partitioned ? run->d_keys : nullptr;
+    const int32_t nk = h->partitioned ? nkeys : 1;
+    const int rc = grouped ? sha_running_grouped(run->d_out_seq, run->d_out_values, n_out, m, d_query, n_query, keys, nk,
+                                                 0, &D, &h->grp, h->a_scratch.p, h->stream)
+                           : sha_running(run->d_out_seq, run->d_out_values, n_out, m, d_query, n_query, keys, nk, 0, &D,
+                                         h->a_scratch.p, h->stream);
+    h->grp_last = grouped && rc == 0 ? 1 : 0;
     if (rc < 0) return fail(h, SH_E_HIP, "aggregate post-pass failed");
     hipEventRecord(h->ev[5], h->stream);
     if (hipEventSynchronize(h->ev[5]) != hipSuccess) return fail(h, SH_E_HIP, "aggregate post-pass failed");
@@ -1614,6 +1622,7 @@ int agg_post(sh_handle* h, sh_device_run* run, int32_t nkeys, const int32_t* d_q
     hipEventElapsedTime(&ms, h->ev[4], h->ev[5]);
     h->times.emit_ms += ms;
     h->times.total_ms += ms;
+    h->agg_post_ms = ms;
     h->agg_last = rc == 0 ? 1 : 2;
     return rc;
 }

@@ -26,6 +26,7 @@
 #include "sh_agg_seq.h"
 #include "sh_bucket_plan.h"
 #include "sh_device.h"
+#include "sh_group.h"
 #include "sh_having.h"
 #include "sh_jit.h"
 #include "sh_jmap.h"
@@ -458,6 +459,13 @@ struct sh_handle {
     DevBuf rl_d_rules;
     RowStage rl;
     CarryTab rl_tab;
+    // ---- `group by` behind the fast engines in bulk runs (sh_group.h): every grouping
+    // query's group values as row positions; the aggregate post-pass (agg_post) then
+    // segments by them. grp_last: the grouped post-pass produced the last run's rows
+    bool grp_on = false;
+    sha_groups grp{};
+    int grp_last = 0;
+    double agg_post_ms = 0.0;  // device time of the last run's aggregate post-pass (agg_post)
     std::vector<int32_t> out_types;  // per select position over the queries (-2: types differ)
     uint64_t fp = 0;                 // compiled-program fingerprint (snapshot images)
 };
@@ -599,6 +607,9 @@ int shx_jit_compile(sh_handle* h);
 int shx_bucket_status(sh_handle* h);
 int shx_seq3_status(sh_handle* h);
 int shx_agg_status(sh_handle* h);
+int shx_group_status(sh_handle* h);
+int shx_group_compiled(sh_handle* h);
+double shx_agg_post_ms(sh_handle* h);
 int shx_having_status(sh_handle* h);
 int shx_having_rows(sh_handle* h, int64_t* rows_in, int64_t* rows_kept);
 double shx_having_ms(sh_handle* h);

@@ -200,6 +200,17 @@ class DeviceRunner:
         streaming step, and a bulk run whose additions would round), 0 none."""
         return lib().shx_agg_status(self.handle.h)
 
+    def group_status(self):
+        """1: the grouped aggregate post-pass (sh_group.hip + sh_agg.hip) produced the
+        last run's rows under `group by`, 0: the select does not group, or the general
+        engine's selector applied the clause."""
+        return lib().shx_group_status(self.handle.h)
+
+    def agg_post_ms(self):
+        """device time of the last run's aggregate post-pass launches (grouped or not;
+        its last call when the run made several), ms; 0 when it did not run"""
+        return lib().shx_agg_post_ms(self.handle.h)
+
     def having_status(self):
         """1: the device row filter (sh_having.hip) applied the output-only `having`
         of the last run, 0: there is none, or the general engine's selector did."""
